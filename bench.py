@@ -20,9 +20,26 @@ the timed region; the host-staged (PCIe-inclusive) cycles are measured after
 it and reported apart.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4]
+                  [--dump-outputs DIR] [--full]
 
 The default workload is C3 (100M tets, metric + level set + velocity, the
 north-star configuration of BASELINE.json, one GPU).
+
+A plain run does what the headline figure needs and no more: it builds the
+case, uploads it, warms up, times the K steps and prints the result line.
+--full adds every other leg after (the CPU baseline: before) the timed region:
+the CPU node baseline, the locate / lane statistics of the last step, the step
+on an already prepared background, the sequential-semantics step, the shipped
+binding's configuration and the host-staged (PCIe-inclusive) cycles; --no-cpu,
+--no-pcie and --no-seq drop single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of
+PMMG_interpMetricsAndFields receives it: the interpolated metric and fields of
+every group, DIR/g<group>_sol<i>.npy (float64, one row per new vertex), and
+the rows' vertex indices DIR/g<group>_rows.npy.  Outputs above the size cap
+are written as a fixed, seeded sample of their rows (the same rows in every
+run).  The inputs are seeded: two runs with the same arguments transfer the
+same case.
 
 N > 1: launched by torch.distributed.run, one rank per GPU; every rank owns its
 own group (ParMmg groups shard with no data-path collective: weak scaling);
@@ -435,12 +452,45 @@ def binding_cycle(m, x, t, tv, sols, local: int, iters: int = 3) -> dict:
                       f"({MMG_POINT.itemsize} / {MMG_TETRA.itemsize} B)"}
 
 
+DUMP_CAP_BYTES = 48 << 20   # all files of one --dump-outputs run together
+
+
+def dump_outputs(trs, directory: str, rank: int, world: int) -> dict:
+    """The last step's interpolated metric and fields of every group of this
+    rank as .npy files (float64): all rows when they fit DUMP_CAP_BYTES, else
+    the same seeded sample of rows in every run."""
+    os.makedirs(directory, exist_ok=True)
+    per_row = sum(8 * (sum(g.sizes) + 1) for g in trs)
+    files = []
+    for gi, g in enumerate(trs):
+        n = g.npts
+        keep = min(n, DUMP_CAP_BYTES // per_row)
+        rows = np.arange(n, dtype=np.int64)
+        if keep < n:
+            rows = np.sort(np.random.default_rng(20250117 + gi).choice(n, keep, replace=False))
+        r = g.download(sols_only=True)
+        pre = (f"r{rank}_" if world > 1 else "") + f"g{gi}_"
+        np.save(os.path.join(directory, pre + "rows.npy"), rows.astype(np.float64))
+        files.append(pre + "rows.npy")
+        for i, a in enumerate(r.sols):
+            np.save(os.path.join(directory, pre + f"sol{i}.npy"), np.ascontiguousarray(a[rows], np.float64))
+            files.append(pre + f"sol{i}.npy")
+    return {"dir": directory, "files": files, "rows_per_group": int(keep),
+            "sampled": bool(keep < trs[0].npts)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="C3", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: CPU baseline, locate statistics, "
+                         "resident-background steps, sequential semantics, binding configuration, "
+                         "host-staged cycles (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's interpolated metric and fields as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-pcie", action="store_true",
                     help="skip the host-staged (PCIe-inclusive) leg measured after the timed region")
@@ -461,6 +511,12 @@ def main():
                     help="N>1 process group backend (nccl = RCCL; gloo only to rehearse "
                          "the multi-rank path, e.g. several ranks on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # the legs beside the headline figure run under --full only
+    want_cpu = args.full and not args.no_cpu
+    want_pcie = args.full and not args.no_pcie
+    want_seq = args.full and not args.no_seq
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -485,7 +541,7 @@ def main():
     phase("build (libraries rebuilt only when stale)")
     build.build_meshgen()
     build.build_transfer()
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and want_cpu:
         build.build_oracle()
 
     cfg = CONFIGS[args.config]
@@ -501,7 +557,7 @@ def main():
     # the CPU baseline first: its worker processes are forked before this
     # process touches the GPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and want_cpu:
         m, x, t, sols, _ = cases[0]
         phase("cpu baseline (forked oracle processes)")
         cpu = cpu_baseline_node(m, x, t, sols)
@@ -557,32 +613,39 @@ def main():
     el = time.perf_counter() - t0
     k_ms = {name: tr.kernel_ms(i) for i, name in enumerate(["hint", "vol", "bdy", "exhaustive", "total",
                                                             "derive"])}
-    st = tr.locate_stats()
-    st["volume_waves"] = tr.wave_stats(0)
-    from parmmg_amd import mesh as M
-    st["wrec_escapes"] = M.wrec_escapes(m)
-    st["wrec_far_fields"], st["wrec_tets_with_far_fields"] = M.wrec_far_fields(m)
-    # the walk's record format (pmx_capi.hip fill_vol_args: 32-B records above
-    # 1/16 of the tets with a far neighbour field)
-    # (r06: the compact records only when the upload builds them,
-    # PMX_WALK_RECORDS=compact; default the 32-B records, no per-background pass)
-    compact = os.environ.get("PMX_WALK_RECORDS") == "compact"
-    st["walk_records"] = "24-B compact" if compact and st["wrec_tets_with_far_fields"] * 16 <= m.ne else "32-B"
-    # the same step on a background already prepared by an earlier step (what
-    # repeated steps on one background cost; reported, never `value`)
-    sync()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(flags=0)
-    sync()
-    resident_ms = (time.perf_counter() - t1) / args.steps * 1e3
+    # the last timed step's results, before any other leg runs a step
+    dumped = None
+    if args.dump_outputs:
+        phase("dump outputs")
+        dumped = dump_outputs(trs, args.dump_outputs, rank, world)
+    st = resident_ms = None
+    if args.full:
+        st = tr.locate_stats()
+        st["volume_waves"] = tr.wave_stats(0)
+        st["wrec_escapes"] = M.wrec_escapes(m)
+        st["wrec_far_fields"], st["wrec_tets_with_far_fields"] = M.wrec_far_fields(m)
+        # the walk's record format (pmx_capi.hip fill_vol_args: 32-B records above
+        # 1/16 of the tets with a far neighbour field)
+        # (r06: the compact records only when the upload builds them,
+        # PMX_WALK_RECORDS=compact; default the 32-B records, no per-background pass)
+        compact = os.environ.get("PMX_WALK_RECORDS") == "compact"
+        st["walk_records"] = ("24-B compact" if compact and st["wrec_tets_with_far_fields"] * 16 <= m.ne
+                              else "32-B")
+        # the same step on a background already prepared by an earlier step (what
+        # repeated steps on one background cost; reported, never `value`)
+        sync()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(flags=0)
+        sync()
+        resident_ms = (time.perf_counter() - t1) / args.steps * 1e3
 
     # the reference's sequential semantics (PMX_RUN_SEQUENTIAL_SURFACE |
     # _VOLUME, bit-exact against the oracle's sequential run in tests/): their
     # cost, and how many points the default step answers differently --
     # another tria / edge / vertex on the surface, another tet in the volume
     seq = None
-    if world == 1 and not args.no_seq and not args.no_new_tets:
+    if world == 1 and want_seq and not args.no_new_tets:
         phase("sequential-semantics step")
         sync()
         tr.run(flags=N.RUN_FRESH_BACKGROUND)
@@ -612,7 +675,7 @@ def main():
     # device face matching of the background -- reported beside ms_per_step,
     # never `value`
     devadj = None
-    if world == 1 and not args.no_pcie:
+    if world == 1 and want_pcie:
         phase("FRESH steps with device face matching")
         sync()
         tr.upload_background(m, sols, 0, adja=False)
@@ -634,7 +697,7 @@ def main():
     # host-staged rate (ParMmg's adapter path: host buffers in and out), measured
     # after the timed region and never reported as `value`
     pcie = None
-    if world == 1 and not args.no_pcie:
+    if world == 1 and want_pcie:
         phase("host-staged cycles")
         pcie = pcie_inclusive(tr, m, x, t, sols)
         pcie["resident_cycle"] = resident_cycle(m, sols, cfg, local)
@@ -713,10 +776,13 @@ def main():
             "not_in_ms": "host packing and PCIe (pcie_inclusive); nothing the device runs per "
                          "upload is outside the step",
             "binding_configuration": devadj},
-        "resident_background_ms_per_step": resident_ms,
         "step_alg_GBs": B_all / (ms * 1e-3) / 1e9,
-        "locate": st,
     }
+    if args.full:
+        out["resident_background_ms_per_step"] = resident_ms
+        out["locate"] = st
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if cpu is not None:
         if pcie is not None:
             # what ParMmg sees (the binding's two seams per iteration, host

@@ -14,12 +14,12 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 out=gpurun_out/prof_$tag
 mkdir -p $out
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $out/trace -o run -- \
-  python3 bench.py --no-cpu --no-pcie $args > $out/trace.log 2>&1 || { echo "trace failed rc=$?"; exit 2; }
+  python3 bench.py --full --no-cpu --no-pcie $args > $out/trace.log 2>&1 || { echo "trace failed rc=$?"; exit 2; }
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD"; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $grp -f csv -d $out/pmc$i -o run -- \
-    python3 bench.py --no-cpu --no-pcie --steps 5 --warmup 1 $args > $out/pmc$i.log 2>&1
+    python3 bench.py --full --no-cpu --no-pcie --steps 5 --warmup 1 $args > $out/pmc$i.log 2>&1
   rc=$?
   echo "pmc$i [$grp] rc=$rc"
   [ $rc -eq 0 ] || exit 3

@@ -18,7 +18,7 @@ for grp in \
   "SQ_WAVES SQ_LEVEL_WAVES SQ_INST_LEVEL_VMEM SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_CYCLES"; do
   i=$((i+1))
   timeout -s KILL 90 rocprofv3 --pmc $grp --kernel-include-regex "k_walk|k_locate_vol|k_hint" -f csv -d $out/pmc$i -o run -- \
-    python3 bench.py --no-cpu --steps 3 --warmup 1 $args > $out/pmc$i.log 2>&1
+    python3 bench.py --full --no-cpu --steps 3 --warmup 1 $args > $out/pmc$i.log 2>&1
   rc=$?
   echo "pmc$i [$grp] rc=$rc"
   [ $rc -eq 0 ] || exit 3
