@@ -124,6 +124,16 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *old_mesh,
 /* ---- new points -------------------------------------------------------- */
 int pmx_upload_points(pmx_ctx *ctx, const pmx_points_view *pts);
 
+/* Source vertices of the new points (ParMmg's USE_POINTMAP build: Mmg gives
+ * every new point the index of the background vertex it descends from,
+ * MMG5_Point.src, seeded src = k before the remesh, src/libparmmg1.c:667-670).
+ * Entry ip at (const char*)src + ip*stride, ip = first..last of the last
+ * points view; pass &mesh->point[0].src, sizeof(MMG5_Point).  After
+ * pmx_upload_points, kept until the next pmx_upload_points; src == NULL
+ * forgets them.  Returns 0 when no points are uploaded.  Read by a pmx_run
+ * with PMX_RUN_POINTMAP. */
+int pmx_upload_point_sources(pmx_ctx *ctx, const int *src, int64_t stride);
+
 /* ---- the hot path (device resident) ------------------------------------ */
 typedef struct {
   int    hint_stride;              /* hint grid built from every k-th tet,
@@ -172,6 +182,20 @@ typedef struct {
 #define PMX_RUN_DEBUG_BARRIER_TIMEOUT 0x100 /* test hook: the fallback's grid
                                          barriers do not wait (the step must
                                          then fail, never return silently)   */
+#define PMX_RUN_POINTMAP 0x200       /* every walk starts from its point's
+                                         source vertex (pmx_upload_point_sources)
+                                         as with the reference's USE_POINTMAP
+                                         (PMMG_locate_setStart, src/locate_pmmg.c:
+                                         931-986; src/interpmesh_pmmg.c:552-554,
+                                         602-604): a surface point from the
+                                         smallest tria holding the vertex, a
+                                         volume point from the smallest valid
+                                         tet holding it; element 1 when the
+                                         source is outside 1..np of the
+                                         background or no element holds it.  No
+                                         hint grid is built.  Fails (0) without
+                                         uploaded sources, and with either
+                                         PMX_RUN_SEQUENTIAL_* flag              */
 #define PMX_RUN_EAGER_DOWNLOAD   0x20 /* the step's fields start down into
                                          pinned staging as soon as it ends
                                          (overlapping the host work that
@@ -237,6 +261,11 @@ int pmx_device_free(pmx_ctx *ctx, void *p);
 int pmx_device_download(pmx_ctx *ctx, void *host, const void *dev, size_t bytes);
 /* and the other way (e.g. an empty partial record of a rank without a group) */
 int pmx_device_upload(pmx_ctx *ctx, void *dev, const void *host, size_t bytes);
+/* The first-incident-element maps of the last PMX_RUN_POINTMAP step's
+ * background build: atomics[0] / atomics[1] = atomicMin operations the tet /
+ * tria pass issued (a lane skips its atomic when the slot already holds a
+ * smaller element), of 4 ne / 3 nt candidates. */
+int pmx_pointmap_stats(pmx_ctx *ctx, int64_t atomics[2]);
 /* Inspection: copy the volume hint grid of the last run to host (cap cells);
  * returns the number of cells (0 on error). */
 int64_t pmx_debug_hint_grid(pmx_ctx *ctx, int *host, int64_t cap);
@@ -268,7 +297,8 @@ double pmx_topo_ms(pmx_ctx *ctx);
 
 /* Kernel timing of the last pmx_run with opts.timing != 0, in ms:
  * which = 0 hint build, 1 volume locate+interp, 2 surface locate+interp,
- * 3 exhaustive fallback, 4 total. */
+ * 3 exhaustive fallback, 4 total, 5 derived data, 6 the first-incident-element
+ * maps of a PMX_RUN_POINTMAP step (0 when the step built none). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -299,6 +329,17 @@ int PMX_interpMetricsAndFields(pmx_ctx *ctx, int ngrp, pmx_group *grps,
  * (pmx_new_mesh_qual_synced).  Errors in pmx_last_error(ctxs[0]). */
 int PMX_interpMetricsAndFields_groups(pmx_ctx *const *ctxs, int ngrp, pmx_group *grps,
                                       const int *permNodGlob, int inputMet);
+
+/* The same with source vertices (ParMmg built with USE_POINTMAP): group g's
+ * walks start from srcs[g] (pmx_upload_point_sources + PMX_RUN_POINTMAP).
+ * srcs == NULL, or an entry with src == NULL: the hint grids for that group. */
+typedef struct {
+  const int *src;     /* &mesh->point[0].src */
+  int64_t    stride;  /* sizeof(MMG5_Point)  */
+} pmx_point_sources;
+int PMX_interpMetricsAndFields_groups_src(pmx_ctx *const *ctxs, int ngrp, pmx_group *grps,
+                                          const pmx_point_sources *srcs, const int *permNodGlob,
+                                          int inputMet);
 
 /* PMMG_copyMetricsAndFields_point (src/interpmesh_pmmg.c:432-446) on the
  * caller's host arrays (a host loop: nothing to do on the device). Old-point

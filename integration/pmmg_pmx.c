@@ -147,12 +147,23 @@ int PMMG_interpMetricsAndFields(PMMG_pParMesh parmesh, int *permNodGlob) {
   int ngrp = parmesh->ngrp, igrp, j, ier;
   pmx_group *g;
   pmx_sol_view *sv;
+#ifdef USE_POINTMAP
+  /* Mmg's point map: every new point's source vertex in the old mesh
+   * (MMG5_Point.src, seeded at src/libparmmg1.c:667-670) starts its walk, as
+   * the reference's own USE_POINTMAP build does (src/interpmesh_pmmg.c:528-532) */
+  pmx_point_sources *ps;
+#endif
   pmx_ctx **ctxs = pmx_groups(parmesh, ngrp > 0 ? ngrp : 1);
   if (!ctxs) return 0;
   for (igrp = 0; igrp < PMMG_pmx_ngrp; igrp++) PMMG_pmx_state[igrp].valid = 0;
   PMMG_CALLOC(parmesh, g, ngrp, pmx_group, "pmx groups", return 0);
   PMMG_CALLOC(parmesh, sv, ngrp * 2 * (PMX_MAX_SOLS + 1), pmx_sol_view, "pmx sols",
               PMMG_DEL_MEM(parmesh, g, pmx_group, "pmx groups"); return 0);
+#ifdef USE_POINTMAP
+  PMMG_CALLOC(parmesh, ps, ngrp, pmx_point_sources, "pmx sources",
+              PMMG_DEL_MEM(parmesh, sv, pmx_sol_view, "pmx sols");
+              PMMG_DEL_MEM(parmesh, g, pmx_group, "pmx groups"); return 0);
+#endif
   for (igrp = 0; igrp < ngrp; igrp++) {
     PMMG_pGrp G = &parmesh->listgrp[igrp], O = &parmesh->old_listgrp[igrp];
     MMG5_pMesh mesh = G->mesh;
@@ -160,6 +171,9 @@ int PMMG_interpMetricsAndFields(PMMG_pParMesh parmesh, int *permNodGlob) {
                  *fl = met + 2, *ofl = fl + PMX_MAX_SOLS;
     if (mesh->nsols > PMX_MAX_SOLS) {
       fprintf(stderr, "  ## Error: %s: more than %d solution fields.\n", __func__, PMX_MAX_SOLS);
+#ifdef USE_POINTMAP
+      PMMG_DEL_MEM(parmesh, ps, pmx_point_sources, "pmx sources");
+#endif
       PMMG_DEL_MEM(parmesh, sv, pmx_sol_view, "pmx sols");
       PMMG_DEL_MEM(parmesh, g, pmx_group, "pmx groups");
       return 0;
@@ -176,8 +190,16 @@ int PMMG_interpMetricsAndFields(PMMG_pParMesh parmesh, int *permNodGlob) {
     g[igrp].fields = fl; g[igrp].old_fields = ofl; g[igrp].nsols = mesh->nsols;
     g[igrp].hsiz = mesh->info.hsiz;
     view_mesh(O->mesh, &g[igrp].old_mesh);
+#ifdef USE_POINTMAP
+    ps[igrp].src = &mesh->point[0].src;  ps[igrp].stride = sizeof(MMG5_Point);
+#endif
   }
+#ifdef USE_POINTMAP
+  ier = PMX_interpMetricsAndFields_groups_src(ctxs, ngrp, g, ps, permNodGlob, parmesh->info.inputMet);
+  PMMG_DEL_MEM(parmesh, ps, pmx_point_sources, "pmx sources");
+#else
   ier = PMX_interpMetricsAndFields_groups(ctxs, ngrp, g, permNodGlob, parmesh->info.inputMet);
+#endif
   if (!ier) pmx_fail(ctxs[0], __func__);
   /* resident only where the group's context ran a step: a group with nothing
    * to locate (no metric and no field, or -hsiz and no field, reference

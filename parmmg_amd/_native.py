@@ -70,6 +70,7 @@ RUN_DEBUG_BARRIER_TIMEOUT = 0x100
 RUN_EAGER_DOWNLOAD = 0x20
 RUN_SEQUENTIAL_SURFACE = 0x40
 RUN_SEQUENTIAL_VOLUME = 0x80
+RUN_POINTMAP = 0x200
 
 
 class Group(C.Structure):
@@ -79,6 +80,11 @@ class Group(C.Structure):
         ("hsiz", C.c_double),
         ("old_mesh", MeshView), ("old_met", C.POINTER(SolView)), ("old_fields", C.POINTER(SolView)),
     ]
+
+
+class PointSources(C.Structure):
+    """pmx_point_sources: one group's source vertices (MMG5_Point.src)."""
+    _fields_ = [("src", iptr), ("stride", i64)]
 
 
 class QualStats(C.Structure):
@@ -151,6 +157,8 @@ SIGNATURES = {
     "pmx_device_info": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "pmx_upload_background": (C.c_int, [C.c_void_p, C.POINTER(MeshView), C.c_int, C.POINTER(SolView), C.c_int]),
     "pmx_upload_points": (C.c_int, [C.c_void_p, C.POINTER(PointsView)]),
+    "pmx_upload_point_sources": (C.c_int, [C.c_void_p, iptr, i64]),
+    "pmx_pointmap_stats": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
     "pmx_run": (C.c_int, [C.c_void_p, C.POINTER(RunOpts)]),
     "pmx_download": (C.c_int, [C.c_void_p, C.POINTER(SolView), i64, iptr, iptr, iptr]),
     "pmx_download_starts": (C.c_int, [C.c_void_p, iptr, i64]),
@@ -176,6 +184,8 @@ SIGNATURES = {
     "PMX_interpMetricsAndFields": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Group), iptr, C.c_int]),
     "PMX_interpMetricsAndFields_groups": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Group), iptr,
                                                     C.c_int]),
+    "PMX_interpMetricsAndFields_groups_src": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Group),
+                                                        C.POINTER(PointSources), iptr, C.c_int]),
     "PMX_copyMetricsAndFields_point": (C.c_int, [C.c_void_p, C.POINTER(Group), u16ptr, i64, iptr, C.c_int, C.c_int]),
     "pmx_tetra_qual": (C.c_int, [C.c_void_p, C.c_int, dptr, i64]),
     "pmx_upload_point_tags": (C.c_int, [C.c_void_p, u16ptr, i64]),

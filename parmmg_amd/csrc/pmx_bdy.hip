@@ -33,7 +33,8 @@ struct BdyArgs {
   const int8_t *kind;
   int64_t nq, nt;
   double hausd;
-  const int *grid;     // tria hint grid (shares GridDesc with the tet grid)
+  const int *grid;     // tria hint grid (shares GridDesc with the tet grid); a
+                       // PMX_RUN_POINTMAP step: the start tria of every list entry
   GridDesc g;
   double *out;
   uint8_t *wmask;
@@ -509,14 +510,17 @@ __device__ void finish_bdy(const BdyArgs &A, int64_t i, int k, const Bary &b, in
 
 __device__ int tria_hint(const BdyArgs &A, D3 p);
 
-template <int CAP>
+// PM (PMX_RUN_POINTMAP): the start tria is A.grid's, per list entry
+template <int CAP, bool PM = false>
 __global__ __launch_bounds__(256) void k_locate_bdy(BdyArgs A) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   unsigned s_cnt = 0, s_sum = 0, s_max = 0, s_min = 0xffffffffu;
   if (j < *A.nlist_dev) {
     const int64_t i = A.list[j];
     const D3 p = ld3(A.q, (int)i);
-    const int start = A.seq_start ? A.seq_start[i] : tria_hint(A, p);
+    int start;
+    if constexpr (PM) start = A.grid[j];
+    else start = A.seq_start ? A.seq_start[i] : tria_hint(A, p);
     const int base = A.seq_base ? A.seq_base[i] : (int)(i + 1);
     A.start[i] = start;
     RegState<CAP> s;
@@ -1077,7 +1081,7 @@ bool pmx_ctx::size_tria_grid() {
 }
 
 // the surface kernels' arguments for the step's points (tria hint grid tgd)
-static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a) {
+static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap = false) {
   BdyArgs B{};
   B.xyz = c->d_xyz.p; B.tris = c->d_tris.p; B.trn = c->d_trn.p; B.ntrange = c->d_ntrange.p; B.ntlist = c->d_ntlist.p;
   B.sol = c->d_sol.p; B.sd = a.sd; B.q = c->d_qxyz.p; B.kind = c->d_kind.p; B.nq = c->nq; B.nt = c->nt;
@@ -1087,6 +1091,7 @@ static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a) {
   B.stuck_list = c->d_blist.p; B.stuck_count = c->d_counts.p + 1;
   B.ovf_list = c->d_olist.p; B.ovf_count = c->d_counts.p + 2;
   B.list = c->d_bdylist.p; B.nlist = c->nq_bdy_ub; B.nlist_dev = c->d_nsel.p + 1; B.wstats = c->d_bstat.p;
+  if (pointmap) B.grid = a.grid + a.nq;      // the surface list's start trias (k_cls_write)
   return B;
 }
 
@@ -1095,9 +1100,11 @@ static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a) {
 // sized the workspace for more (the sequential mode's speculative pass, whose
 // walks from the predecessors' trias overflow by the thousand)
 static void launch_bdy_walks(const BdyArgs &B, int *ows, int exp, hipStream_t s, int ovf_threads = OVF_THREADS,
-                             bool hashed = false) {
+                             bool hashed = false, bool pointmap = false) {
   const int64_t nb = (B.nlist + 255) / 256;
-  if (exp == 10)                         // A/B: the r01-r03 8-entry private lists
+  if (pointmap)
+    hipLaunchKernelGGL((k_locate_bdy<BDY_CAP, true>), dim3((unsigned)nb), dim3(256), 0, s, B);
+  else if (exp == 10)                    // A/B: the r01-r03 8-entry private lists
     hipLaunchKernelGGL(k_locate_bdy<BDY_CAP / 2>, dim3((unsigned)nb), dim3(256), 0, s, B);
   else
     hipLaunchKernelGGL(k_locate_bdy<BDY_CAP>, dim3((unsigned)nb), dim3(256), 0, s, B);
@@ -1108,7 +1115,7 @@ static void launch_bdy_walks(const BdyArgs &B, int *ows, int exp, hipStream_t s,
   hipLaunchKernelGGL(k_exh_bdy, dim3(256), dim3(256), 0, s, B);
 }
 
-bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s) {
+bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
   if (nt < 1) { err = "surface points present but the background has no boundary trias"; return false; }
   if (!d_blist.p || d_blist.cap < (size_t)nq) {
     if (d_blist.p) hipFree(d_blist.p);
@@ -1124,18 +1131,18 @@ bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s) {
   }
   // tria hint grid: sized and allocated with the background
   // (pmx_ctx::size_tria_grid), zeroed and built at the head of the surface
-  // path (off the main stream)
-  if (hipMemsetAsync(d_tgrid, 0, sizeof(int) * (size_t)tcells, s) != hipSuccess) {
+  // path (off the main stream); none with point-map starts
+  if (!pointmap && hipMemsetAsync(d_tgrid, 0, sizeof(int) * (size_t)tcells, s) != hipSuccess) {
     err = "tria hint grid memset";
     return false;
   }
-  {
+  if (!pointmap) {
     int64_t nb = (nt + 255) / 256;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_tria_hint_build, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(256), 0, s,
                        d_tris.p, d_xyz.p, nt, d_tgrid, tgd);
   }
-  launch_bdy_walks(bdy_args(this, a), d_ows.p, a.exp, s);
+  launch_bdy_walks(bdy_args(this, a, pointmap), d_ows.p, a.exp, s, OVF_THREADS, false, pointmap);
   return hipGetLastError() == hipSuccess;
 }
 

@@ -26,8 +26,8 @@
 
 // events per recorded step: 0 start, 7 derived data built, 1 hint built,
 // 2 volume walk done, 3/5 surface path start (node -> trias fans) / end (side
-// stream), 6 joined, 4 end
-#define PMX_EV_PER_RUN 8
+// stream), 6 joined, 4 end, 8/9 around the point-map's first-incident maps
+#define PMX_EV_PER_RUN 10
 
 // errors of the calls that work without a context (per host thread)
 static thread_local std::string noctx_err;
@@ -585,6 +585,7 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
   // upload has completed (a failed call must not leave sizes that disagree
   // with the device buffers)
   ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
+  ctx->have_pmap = false;
   ctx->eager_nch = 0;
   ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = false;
   ctx->stat_np = -1;
@@ -810,6 +811,7 @@ int pmx_upload_points(pmx_ctx *ctx, const pmx_points_view *pv) {
   if (!ctx) return 0;
   ctx->have_pts = ctx->ran = false;
   ctx->have_ntet = false;                  // the new tets belong to the points
+  ctx->have_src = false;                   // and so do the source vertices
   Trace tr("points");
   if (ctx->next_topo) {                     // its buffers are about to be reused
     CK(hipStreamSynchronize(ctx->topo));
@@ -943,6 +945,33 @@ int pmx_upload_points(pmx_ctx *ctx, const pmx_points_view *pv) {
   ctx->have_pts = true;
   ctx->have_ntet = ntet > 0;
   ctx->n_ntet = ntet;
+  return 1;
+}
+
+// The new points' source vertices (MMG5_Point.src of a USE_POINTMAP build),
+// packed dense in the pinned arena and sent on the context's stream.  Any int
+// is accepted: a source outside 1..np of the step's background, or one no
+// element holds, starts its walk from element 1 (resolved on the device).
+int pmx_upload_point_sources(pmx_ctx *ctx, const int *src, int64_t stride) {
+  if (!ctx) return 0;
+  if (!ctx->have_pts) { ctx->err = "pmx_upload_point_sources: upload the points first"; return 0; }
+  ctx->have_src = false;
+  if (!src) return 1;
+  if (stride < (int64_t)sizeof(int)) { ctx->err = "pmx_upload_point_sources: bad stride"; return 0; }
+  hipSetDevice(ctx->device);
+  const int64_t n = ctx->nq;
+  if (!dgrow(ctx, ctx->d_qsrc, (size_t)std::max<int64_t>(n, 1))) return 0;
+  if (n) {
+    int *h = (int *)hstage(ctx, (size_t)n * sizeof(int));
+    if (!h) return 0;
+    const char *ps = (const char *)src;
+    const int64_t first = ctx->pts_first;
+    par_for(0, n, [&](int64_t j0, int64_t j1) {
+      for (int64_t j = j0; j < j1; j++) h[j] = *(const int *)(ps + (first + j) * stride);
+    });
+    CK(hipMemcpyAsync(ctx->d_qsrc.p, h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  }
+  ctx->have_src = true;
   return 1;
 }
 
@@ -1134,6 +1163,9 @@ static void fill_vol_args(pmx_ctx *ctx, const SolDesc &sd, const pmx_run_opts &o
       (A.exp != 18 && (uint64_t)ctx->h_nbad[2] * PMX_WREC_FAR_DIV > (uint64_t)std::max<int64_t>(ctx->ne, 1)))
     A.wrec = nullptr;
   A.far = ctx->h_nbad[2] > 0 ? 1 : 0;
+  // point-map starts: no grid; the walks' PM instantiations read the start
+  // elements the classification resolved, passed in its place
+  if (opts.flags & PMX_RUN_POINTMAP) A.grid = ctx->d_pstart.p;
 }
 
 // pmx_run_opts.flags: the public PMX_RUN_* bits, plus the experiment switch
@@ -1145,7 +1177,8 @@ static void fill_vol_args(pmx_ctx *ctx, const SolDesc &sd, const pmx_run_opts &o
 static bool run_flags_valid(int flags, std::string *err) {
   const int pub = PMX_RUN_REFERENCE_WALK | PMX_RUN_NO_INLINE_TIES | PMX_RUN_RECORD_STARTS |
                   PMX_RUN_SERIAL_SURFACE | PMX_RUN_FRESH_BACKGROUND | PMX_RUN_DEBUG_BARRIER_TIMEOUT |
-                  PMX_RUN_EAGER_DOWNLOAD | PMX_RUN_SEQUENTIAL_SURFACE | PMX_RUN_SEQUENTIAL_VOLUME;
+                  PMX_RUN_EAGER_DOWNLOAD | PMX_RUN_SEQUENTIAL_SURFACE | PMX_RUN_SEQUENTIAL_VOLUME |
+                  PMX_RUN_POINTMAP;
   if (flags & ~(pub | (0xff << PMX_RUN_EXP_SHIFT))) {
     *err = "pmx_run: unknown flag bits";
     return false;
@@ -1176,7 +1209,22 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
   if (o) opts = *o;
   if (opts.hint_stride < 0 || opts.max_walk < 0) { ctx->err = "pmx_run: bad options"; return 0; }
   if (!run_flags_valid(opts.flags, &ctx->err)) return 0;
+  // point-map starts (the reference's USE_POINTMAP): every walk from its
+  // point's source vertex.  The sequential modes' speculate-and-replay is
+  // built on carried starts: refused together
+  const bool pm = (opts.flags & PMX_RUN_POINTMAP) != 0;
+  if (pm && (opts.flags & (PMX_RUN_SEQUENTIAL_SURFACE | PMX_RUN_SEQUENTIAL_VOLUME))) {
+    ctx->err = "pmx_run: PMX_RUN_POINTMAP cannot be combined with PMX_RUN_SEQUENTIAL_SURFACE / _VOLUME";
+    return 0;
+  }
+  if (pm && !ctx->have_src) {
+    ctx->err = "pmx_run: PMX_RUN_POINTMAP needs the sources of the current points (pmx_upload_point_sources)";
+    return 0;
+  }
   const int64_t n = ctx->nq;
+  if (pm && (!dgrow(ctx, ctx->d_pstart, (size_t)std::max<int64_t>(2 * n, 1)) ||
+             !dgrow(ctx, ctx->d_pmap, (size_t)(2 * (ctx->np + 1))) || !dgrow(ctx, ctx->d_pmcnt, 2)))
+    return 0;
   const int S = ctx->sd.S;
   if (!dgrow(ctx, ctx->d_out, (size_t)std::max<int64_t>(n * S, 1))) return 0;
   SolDesc sd = ctx->sd;
@@ -1205,7 +1253,7 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
   ZeroRanges z{};
   z.add(ctx->d_wmask.p, n);
   z.add(ctx->d_counts.p, 32 * sizeof(unsigned));
-  z.add(ctx->d_grid.p, ctx->gcells * (int64_t)sizeof(int));
+  if (!pm) z.add(ctx->d_grid.p, ctx->gcells * (int64_t)sizeof(int));
   launch_prologue(z, st);
   // the node -> trias fans (PMMG_precompute_nodeTrias, surface points only)
   // on the side stream from the start of the step: a small radix sort that
@@ -1271,6 +1319,14 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
   if (fresh && !ctx->rederive(st)) return 0;
   if (marks_after_derive && !launch_marks()) return 0;
   if (ev) CK(hipEventRecord(ev[7], st));
+  // the first-incident-element maps: derived background data like the tria
+  // normals, after the records a FRESH step rebuilt, only for a flagged step
+  if (ev) CK(hipEventRecord(ev[8], st));
+  if (pm && (!ctx->have_pmap || fresh)) {
+    launch_pmap_build(ctx->d_tets.p, ctx->ne, ctx->d_tris.p, ctx->nt, ctx->np, ctx->d_pmap.p, ctx->d_pmcnt.p, st);
+    ctx->have_pmap = true;
+  }
+  if (ev) CK(hipEventRecord(ev[9], st));
   // with the marks in the step, the hint build (which does not depend on the
   // points) goes ahead of the classification, beside the marks
   const int stride = opts.hint_stride > 0 ? opts.hint_stride : PMX_HINT_STRIDE;
@@ -1280,6 +1336,7 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     if (!(s == sd.imet && sd.metric_const)) any_interp = true;
   GridDesc g_hint = ctx->grid;
   auto hint_build = [&]() {
+    if (pm) return;                          // no grid: the starts come with the classification
     launch_hint_build(packed ? ctx->d_tets_s.p : nullptr,
                       packed && ctx->samples_sorted ? ctx->d_tets_sk.p : nullptr, ctx->d_tets.p, ctx->ne,
                       stride, ctx->d_grid.p, g_hint, hint_xyz ? nullptr : ctx->d_xyzq.p, ctx->d_xyz.p, st,
@@ -1293,7 +1350,7 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
   const bool hint_first = marks && !marks_late && any_interp;
   if (hint_first) hint_build();
   if (marks && !marks_late) CK(hipStreamWaitEvent(st, ctx->ev_tets, 0));
-  if (!ctx->classify(st, marks && !marks_late)) return 0;
+  if (!ctx->classify(st, marks && !marks_late, pm)) return 0;
   if (sd.metric_const)
     launch_const_metric(ctx->d_kind.p, n, ctx->d_out.p, S, sd.off[sd.imet], sd.size[sd.imet],
                         opts.hsiz, ctx->d_wmask.p, sd.imet, st);
@@ -1318,7 +1375,7 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
         if (!ctx->build_node_trias(side, 0, fresh)) return false;
         ctx->have_csr = true;
       }
-      if (!ctx->launch_bdy(A, side)) return false;
+      if (!ctx->launch_bdy(A, side, pm)) return false;
       if (ev) CK(hipEventRecord(ev[5], side));
       CK(hipEventRecord(ctx->ev_join, side));
       return true;
@@ -1326,19 +1383,19 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     const bool early = A.exp != 9;
     if (early && !fork_surface()) return 0;
     if (!hint_first) hint_build();
-    if (exp == 13 && A.wrec) {
+    if (exp == 13 && A.wrec && !pm) {
       if (!dgrow(ctx, ctx->d_hrec, (size_t)(2 * ctx->gcells))) return 0;
       launch_hint_inline(ctx->d_grid.p, ctx->gcells, ctx->d_wrec.p, ctx->d_hrec.p, st);
       A.hrec = ctx->d_hrec.p;
     }
     if (ev) CK(hipEventRecord(ev[1], st));
     if (!early && !fork_surface()) return 0;
-    if (ctx->nq_vol_ub) launch_walk(A, st);
+    if (ctx->nq_vol_ub) launch_walk(A, st, pm);
     if (ev) CK(hipEventRecord(ev[2], st));
     if (bdy && !serial) {
       CK(hipStreamWaitEvent(st, ctx->ev_join, 0));     // surface path done
     } else if (bdy) {
-      if (!ctx->launch_bdy(A, st)) return 0;
+      if (!ctx->launch_bdy(A, st, pm)) return 0;
       if (ev) CK(hipEventRecord(ev[5], st));
     } else if (ev) {
       CK(hipEventRecord(ev[5], st));
@@ -1374,7 +1431,7 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     if (ev) CK(hipEventRecord(ev[4], st));
   } else if (ev) {
     for (int k = 1; k < PMX_EV_PER_RUN; k++)
-      if (k != 7 && k != 3) CK(hipEventRecord(ev[k], st));
+      if (k != 7 && k != 3 && k != 8 && k != 9) CK(hipEventRecord(ev[k], st));
   }
   CK(hipGetLastError());
   // the step located every live point: the orphans' rows are reset by the
@@ -1765,6 +1822,18 @@ int64_t pmx_debug_hint_grid(pmx_ctx *ctx, int *host, int64_t cap) {
   return ctx->gcells;
 }
 
+int pmx_pointmap_stats(pmx_ctx *ctx, int64_t atomics[2]) {
+  if (!ctx || !atomics) return 0;
+  if (!ctx->have_pmap) { ctx->err = "pmx_pointmap_stats: no PMX_RUN_POINTMAP step on this background"; return 0; }
+  hipSetDevice(ctx->device);
+  CK(hipStreamSynchronize(ctx->stream));
+  unsigned c[2] = {0, 0};
+  CK(hipMemcpy(c, ctx->d_pmcnt.p, sizeof c, hipMemcpyDeviceToHost));
+  atomics[0] = c[0];
+  atomics[1] = c[1];
+  return 1;
+}
+
 int pmx_timing_reset(pmx_ctx *ctx) {
   if (!ctx) return 0;
   ctx->ev_used = 0;
@@ -1772,15 +1841,16 @@ int pmx_timing_reset(pmx_ctx *ctx) {
 }
 
 double pmx_kernel_ms(pmx_ctx *ctx, int which) {
-  if (!ctx || ctx->ev_used == 0 || which < 0 || which > 5) return -1.0;
+  if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
   for (int r = 0; r < ctx->ev_used; r++) {
     hipEvent_t *e = &ctx->events[(size_t)r * PMX_EV_PER_RUN];
     float ms = 0.f;
     // 0 hint (prologue + derived data + hint build), 1 volume walk, 2 surface
-    // path, 3 fallback, 4 total, 5 derived data (prologue included)
-    static const int from[6] = {0, 1, 3, 6, 0, 0}, to[6] = {1, 2, 5, 4, 4, 7};
+    // path, 3 fallback, 4 total, 5 derived data (prologue included), 6 the
+    // point-map's first-incident maps
+    static const int from[7] = {0, 1, 3, 6, 0, 0, 8}, to[7] = {1, 2, 5, 4, 4, 7, 9};
     hipEventElapsedTime(&ms, e[from[which]], e[to[which]]);
     tot += ms;
   }
@@ -1996,6 +2066,7 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   tr.mark("trias");
   // the background invalid until this completes
   ctx->have_bg = ctx->have_derived = ctx->have_tetv = ctx->have_qual = ctx->have_ptag = ctx->have_csr = ctx->have_surf = false;
+  ctx->have_pmap = false;
   ctx->bg_btv = false;                     // records from the new tets (or the caller's adja), not d_btv
   ctx->stat_np = -1;
   const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
@@ -2068,10 +2139,16 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
 
 // the new points' classification and compaction on stream s (the marks, if
 // any, zeroed beforehand)
-bool pmx_ctx::classify(hipStream_t s, bool marks) {
+bool pmx_ctx::classify(hipStream_t s, bool marks, bool pointmap) {
   if (nq < 1) return true;
-  launch_classify(have_qtag ? d_qtag.p : nullptr, marks ? d_qmark.p : nullptr, nq, d_ctile.p, d_kind.p, d_vollist.p, d_bdylist.p,
-                  d_nsel.p, s);
+  const uint16_t *tg = have_qtag ? d_qtag.p : nullptr;
+  const uint8_t *mk = marks ? d_qmark.p : nullptr;
+  if (pointmap) {
+    const PointMapArgs pma{d_qsrc.p, d_pmap.p, d_pmap.p + (np + 1), np, d_pstart.p, d_pstart.p + nq};
+    launch_classify_pointmap(tg, mk, nq, d_ctile.p, d_kind.p, d_vollist.p, d_bdylist.p, d_nsel.p, pma, s);
+  } else {
+    launch_classify(tg, mk, nq, d_ctile.p, d_kind.p, d_vollist.p, d_bdylist.p, d_nsel.p, s);
+  }
   if (hipGetLastError() != hipSuccess) {
     err = "classification: launch failed";
     return false;
@@ -2101,6 +2178,8 @@ void pmx_ctx::free_all() {
   dfree(d_steps); dfree(d_start); dfree(d_edge); dfree(d_vertex); dfree(d_list); dfree(d_found);
   dfree(d_bestk); dfree(d_best); dfree(d_ties); dfree(d_counts); dfree(d_vollist); dfree(d_bdylist);
   dfree(d_vstat); dfree(d_bstat); dfree(d_hrec);
+  dfree(d_qsrc); dfree(d_pstart); dfree(d_pmap); dfree(d_pmcnt);
+  have_src = have_pmap = false;
   dfree(d_sqkey); dfree(d_sqidx); dfree(d_sqint); dfree(d_sqtf); dfree(d_sqpf); dfree(d_sqtv); dfree(d_sqows); dfree(d_sqval);
   dfree(d_sqw);
   dfree(d_sqtmp);

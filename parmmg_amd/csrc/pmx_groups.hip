@@ -51,7 +51,10 @@ static int constant_metric(pmx_ctx *ctx, const pmx_sol_view *met, int64_t first,
 // enqueued, so a group's host staging and upload overlap the steps of the
 // groups before it.  A failing group makes the call fail but the other groups
 // are still processed (reference :715-721); errors go to `ectx`.
-static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_group *grps, int inputMet) {
+// srcs (may be null): group g's source vertices -- its walks then start from
+// them (PMX_RUN_POINTMAP, the reference's USE_POINTMAP build).
+static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_group *grps, int inputMet,
+                         const pmx_point_sources *srcs = nullptr) {
   int ier = 1;
   std::string first_err;
   auto fail = [&](pmx_ctx *c) {
@@ -128,6 +131,10 @@ static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_grou
              (v == "all" || v == "1" ? PMX_RUN_SEQUENTIAL_SURFACE | PMX_RUN_SEQUENTIAL_VOLUME : 0);
     }();
     o.flags |= seqf;
+    if (srcs && srcs[g].src) {
+      if (!pmx_upload_point_sources(X, srcs[g].src, srcs[g].stride)) { fail(X); continue; }
+      o.flags |= PMX_RUN_POINTMAP;
+    }
     if (!pmx_run(X, &o)) { fail(X); continue; }
     // outputs in Mmg layout start at point index `first`
     for (int k = 0; k < ns; k++)
@@ -168,13 +175,19 @@ int PMX_interpMetricsAndFields(pmx_ctx *ctx, int ngrp, pmx_group *grps, const in
 // pmx_new_mesh_qual_synced until that context's next upload.
 int PMX_interpMetricsAndFields_groups(pmx_ctx *const *ctxs, int ngrp, pmx_group *grps,
                                       const int *permNodGlob, int inputMet) {
+  return PMX_interpMetricsAndFields_groups_src(ctxs, ngrp, grps, nullptr, permNodGlob, inputMet);
+}
+
+int PMX_interpMetricsAndFields_groups_src(pmx_ctx *const *ctxs, int ngrp, pmx_group *grps,
+                                          const pmx_point_sources *srcs, const int *permNodGlob,
+                                          int inputMet) {
   (void)permNodGlob;
   if (ngrp < 0 || (ngrp > 0 && (!ctxs || !grps))) return 0;
   for (int g = 0; g < ngrp; g++)
     if (!ctxs[g]) return 0;
   if (ngrp == 0) return 1;
   hipSetDevice(ctxs[0]->device);
-  return interp_groups(ctxs[0], ctxs, ngrp, grps, inputMet);
+  return interp_groups(ctxs[0], ctxs, ngrp, grps, inputMet, srcs);
 }
 
 }  // extern "C"

@@ -87,6 +87,14 @@ struct pmx_ctx {
   DevBuf<unsigned long long> d_xyzq;    // fixed-point grid coordinates (hint centroids)
   DevBuf<Pt4> d_trn;                    // tria unit normals + areas
   DevBuf<int> d_grid;
+  // PMX_RUN_POINTMAP: the first-incident-element maps (k_pmap_tets /
+  // k_pmap_trias), np + 1 words each: [0, np] smallest valid tet holding the
+  // vertex, [np + 1, 2 np + 1] smallest tria (0xffffffff: none).  Derived
+  // background data, built by the first flagged step after an upload (or by
+  // every flagged FRESH step), never by an unflagged one; d_pmcnt[0..1] the
+  // atomics the two passes issued
+  bool have_pmap = false;
+  DevBuf<unsigned> d_pmap, d_pmcnt;
   // statistics only: 16-B connectivity stream, derived on first use
   bool have_tetv = false;
   DevBuf<int4> d_tetv;
@@ -111,6 +119,11 @@ struct pmx_ctx {
   DevBuf<double> d_qxyz;                // new points as uploaded (dense xyz)
   DevBuf<uint8_t> d_qmark;              // orphan marks (points of valid new tets), uploaded when needed
   DevBuf<int> d_nsel;                   // compaction counts: volume, surface
+  // the new points' source vertices (pmx_upload_point_sources; dense, entry
+  // j = view index first + j) and, of a PMX_RUN_POINTMAP step, the resolved
+  // start element per compacted point: [0, nq) volume list, [nq, 2 nq) surface
+  bool have_src = false;
+  DevBuf<int> d_qsrc, d_pstart;
   DevBuf<int2> d_ctile;                 // classification tile counts
   DevBuf<uint4> d_vstat, d_bstat;       // per-wave walk statistics
   DevBuf<uint4> d_hrec;                 // exp 13: hint cells with their start record inline
@@ -240,8 +253,11 @@ struct pmx_ctx {
   bool build_node_trias(hipStream_t s, int force = 0, bool check = false);
   // the new points: kinds, lists (pmx_capi.hip); marks: the orphan marks
   // (d_qmark) classify points in no valid new tet as KIND_ORPH
-  bool classify(hipStream_t s, bool marks = false);
-  bool launch_bdy(const VolArgs &a, hipStream_t s);
+  // pointmap: also the start element of every compacted point from its
+  // source vertex (d_qsrc through d_pmap into d_pstart)
+  bool classify(hipStream_t s, bool marks = false, bool pointmap = false);
+  // pointmap: a.grid holds the start elements (no tria hint grid is built)
+  bool launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap = false);
   // PMX_RUN_SEQUENTIAL_SURFACE / _VOLUME after the step's passes, on stream s
   // (synchronises the host: a replayed query that ends stuck is scanned by a
   // launch of its own; pmx_bdy.hip)

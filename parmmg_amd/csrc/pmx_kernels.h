@@ -33,7 +33,11 @@ struct VolArgs {
   const double *q;              // new points as uploaded, dense x y z (0-based)
   const int8_t *kind;
   int64_t nq, ne;
-  const int *grid;
+  const int *grid;              // hint grid, cell -> tet.  A PMX_RUN_POINTMAP step has none: it
+                                // passes the start elements resolved by k_cls_write here,
+                                // [0, nq) per volume list entry, [nq, 2 nq) per surface list
+                                // entry, read by the PM instantiations of the walks (the
+                                // argument block, and with it every default kernel, unchanged)
   const uint4 *hrec;            // exp 13: the hint cells with their start record inline
   GridDesc g;
   double *out;
@@ -87,7 +91,8 @@ void launch_hint_inline(const int *grid, int64_t cells, const WRec *wr, uint4 *h
 // (PMMG_precompute_triaNormals, src/locate_pmmg.c:68-90), one launch
 void launch_bg_derive(const double *xyz, int64_t np, GridDesc g, unsigned long long *xyzq,
                       const TriRec *tris, int64_t nt, Pt4 *trn, hipStream_t s);
-void launch_walk(const VolArgs &a, hipStream_t s);
+// pointmap: the PM instantiations (a.grid holds the start elements)
+void launch_walk(const VolArgs &a, hipStream_t s, bool pointmap = false);
 void launch_exhaustive(const ExhArgs &e, const VolArgs &v, int blocks, hipStream_t s);
 void launch_const_metric(const int8_t *kind, int64_t nq, double *out, int S, int off, int size,
                          double hsiz, uint8_t *wmask, int imet, hipStream_t s);
@@ -123,6 +128,25 @@ void launch_patch_rows(const int4 *ent, const double *vals, int64_t n, int S, do
 inline int64_t cls_tiles(int64_t n) { return (n + CLS_TILE - 1) / CLS_TILE; }
 void launch_classify(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind, int *vlist,
                      int *blist, int *nsel, hipStream_t s);
+// PMX_RUN_POINTMAP.  The first-incident-element maps of a background
+// (PMMG_locate_setStart, src/locate_pmmg.c:931-986, whose loops keep the
+// first index that reaches a vertex): map[p] = the smallest valid tet
+// (v[0] > 0) holding vertex p, map[np + 1 + p] = the smallest tria, 0xffffffff
+// when none; 2 (np + 1) words, filled here.  cnt[0..1]: atomics issued.
+void launch_pmap_build(const TetRec *tets, int64_t ne, const TriRec *tris, int64_t nt, int64_t np,
+                       unsigned *map, unsigned *cnt, hipStream_t s);
+// launch_classify that also carries the source vertices src[0..n) through the
+// compaction: vstart[j] / bstart[j] = the start element of the j-th volume /
+// surface point, vmap / tmap of its source, 1 when the source is outside
+// 1..np or no element holds it
+struct PointMapArgs {
+  const int *src;
+  const unsigned *vmap, *tmap;
+  int64_t np;
+  int *vstart, *bstart;
+};
+void launch_classify_pointmap(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind,
+                              int *vlist, int *blist, int *nsel, const PointMapArgs &pm, hipStream_t s);
 
 void launch_build_tetrec(const int4 *tv, const int *adja, int64_t ne, int stride, TetRec *tets, int4 *sample,
                          hipStream_t s);

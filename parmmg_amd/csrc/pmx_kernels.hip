@@ -1074,11 +1074,19 @@ __global__ __launch_bounds__(256) void k_cls_count(const uint16_t *__restrict__ 
 // the wave then writes its list entries in 16 coalesced ballot sub-rounds.
 // Tile base = sum of the previous tiles' counts, summed again by every
 // workgroup (a few KB of L2 reads instead of a third launch).
+// PM (PMX_RUN_POINTMAP): the point's source vertex goes through the
+// compaction with it -- the start element of list entry j is resolved here
+// (one coalesced read of the sources, one gather of the map), so that the
+// walks read a coalesced int.
+// (The point-map arguments are a parameter pack: empty for the default
+// kernel, whose argument block and code stay what they were.)
+__device__ __forceinline__ const PointMapArgs &cls_pm(const PointMapArgs &a) { return a; }
+template <bool PM, class... PMA>
 __global__ __launch_bounds__(256) void k_cls_write(const uint16_t *__restrict__ tag,
                                                    const uint8_t *__restrict__ mark, int64_t n,
                                                    const int2 *__restrict__ tcnt, int8_t *__restrict__ kind,
                                                    int *__restrict__ vlist, int *__restrict__ blist,
-                                                   int *__restrict__ nsel) {
+                                                   int *__restrict__ nsel, PMA... pma) {
   __shared__ int2 red[4];
   __shared__ int2 wc[4];
   __shared__ uint4 lk[256];                   // the round's 4096 kinds
@@ -1130,6 +1138,17 @@ __global__ __launch_bounds__(256) void k_cls_write(const uint16_t *__restrict__ 
       const unsigned long long bv = __ballot(k == KIND_VOL), bb = __ballot(k == KIND_BDY);
       if (k == KIND_VOL) vlist[ov + __popcll(bv & below)] = (int)(r0 + p);
       else if (k == KIND_BDY) blist[ob + __popcll(bb & below)] = (int)(r0 + p);
+      if constexpr (PM) {
+        const PointMapArgs &pm = cls_pm(pma...);
+        if (k == KIND_VOL || k == KIND_BDY) {
+          const int sv = pm.src[r0 + p];
+          unsigned e = 0xffffffffu;
+          if (sv >= 1 && (int64_t)sv <= pm.np) e = (k == KIND_VOL ? pm.vmap : pm.tmap)[sv];
+          const int st = e == 0xffffffffu ? 1 : (int)e;     // the reference's initial start
+          if (k == KIND_VOL) pm.vstart[ov + __popcll(bv & below)] = st;
+          else pm.bstart[ob + __popcll(bb & below)] = st;
+        }
+      }
       ov += __popcll(bv);
       ob += __popcll(bb);
     }
@@ -1146,6 +1165,77 @@ void launch_classify(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tc
   if (n < 1) return;
   const unsigned nt = (unsigned)cls_tiles(n);
   hipLaunchKernelGGL(k_cls_count, dim3(nt), dim3(256), 0, s, tag, mk, n, tcnt);
-  hipLaunchKernelGGL(k_cls_write, dim3(nt), dim3(256), 0, s, tag, mk, n, (const int2 *)tcnt, kind, vlist,
+  hipLaunchKernelGGL((k_cls_write<false>), dim3(nt), dim3(256), 0, s, tag, mk, n, (const int2 *)tcnt, kind, vlist,
                      blist, nsel);
+}
+void launch_classify_pointmap(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind,
+                              int *vlist, int *blist, int *nsel, const PointMapArgs &pm, hipStream_t s) {
+  if (n < 1) return;
+  const unsigned nt = (unsigned)cls_tiles(n);
+  hipLaunchKernelGGL(k_cls_count, dim3(nt), dim3(256), 0, s, tag, mk, n, tcnt);
+  hipLaunchKernelGGL((k_cls_write<true, PointMapArgs>), dim3(nt), dim3(256), 0, s, tag, mk, n, (const int2 *)tcnt,
+                     kind, vlist, blist, nsel, pm);
+}
+
+// ---- PMX_RUN_POINTMAP: the first-incident-element maps ---------------------
+//
+// vmap[p] = min{k : tets[k].v[0] > 0, p in tets[k].v}, tmap[p] = min{k : p in
+// tris[k].v} -- what the reference's loops leave in ppt->s / ppt->tmp
+// (PMMG_locate_setStart keeps the first index that reaches a vertex).  The
+// exact minimum needs atomicMin: a plain store would make the start, and with
+// it the surface answers, vary from run to run.  A lane reads the slot first
+// and issues the atomic only when its element is smaller (the slots only ever
+// decrease, so a stale read costs an atomic, never the minimum).  Measured at
+// C3: the read filters 70 % of the 4 ne candidates in the lattice numbering
+// (the tets in flight together around a vertex's first cell all issue), 90 %
+// in a shuffled one.  The atomics issued are counted
+// per wave (cnt), one add per wave that issued any.
+__device__ __forceinline__ void pmap_min(unsigned *__restrict__ map, int v, int64_t np, unsigned k,
+                                         unsigned &issued) {
+  if (v < 1 || (int64_t)v > np) return;
+  if (__hip_atomic_load(map + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > k) {
+    atomicMin(map + v, k);
+    issued++;
+  }
+}
+__device__ __forceinline__ void pmap_count(unsigned issued, unsigned *cnt) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) issued += __shfl_xor(issued, o, 64);
+  if ((threadIdx.x & 63) == 0 && issued) atomicAdd(cnt, issued);
+}
+__global__ __launch_bounds__(256) void k_pmap_tets(const TetRec *__restrict__ tets, int64_t ne, int64_t np,
+                                                   unsigned *__restrict__ vmap, unsigned *__restrict__ cnt) {
+  unsigned issued = 0;
+  const int64_t st = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= ne; k += st) {
+    const int4 v = *reinterpret_cast<const int4 *>(tets + k);
+    if (v.x <= 0) continue;                              // deleted tet
+    pmap_min(vmap, v.x, np, (unsigned)k, issued);
+    pmap_min(vmap, v.y, np, (unsigned)k, issued);
+    pmap_min(vmap, v.z, np, (unsigned)k, issued);
+    pmap_min(vmap, v.w, np, (unsigned)k, issued);
+  }
+  pmap_count(issued, cnt);
+}
+__global__ __launch_bounds__(256) void k_pmap_trias(const TriRec *__restrict__ tris, int64_t nt, int64_t np,
+                                                    unsigned *__restrict__ tmap, unsigned *__restrict__ cnt) {
+  unsigned issued = 0;
+  const int64_t st = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t k = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt; k += st) {
+    const int4 v = *reinterpret_cast<const int4 *>(tris + k);    // v[0..2], pad
+    pmap_min(tmap, v.x, np, (unsigned)k, issued);
+    pmap_min(tmap, v.y, np, (unsigned)k, issued);
+    pmap_min(tmap, v.z, np, (unsigned)k, issued);
+  }
+  pmap_count(issued, cnt);
+}
+void launch_pmap_build(const TetRec *tets, int64_t ne, const TriRec *tris, int64_t nt, int64_t np,
+                       unsigned *map, unsigned *cnt, hipStream_t s) {
+  unsigned *vmap = map, *tmap = map + (np + 1);
+  hipMemsetAsync(map, 0xff, (size_t)(2 * (np + 1)) * sizeof(unsigned), s);
+  hipMemsetAsync(cnt, 0, 2 * sizeof(unsigned), s);
+  const int64_t nbt = std::min<int64_t>((ne + 255) / 256, 65536);
+  const int64_t nbs = std::min<int64_t>((nt + 255) / 256, 4096);
+  if (nbt > 0) hipLaunchKernelGGL(k_pmap_tets, dim3((unsigned)nbt), dim3(256), 0, s, tets, ne, np, vmap, cnt);
+  if (nbs > 0) hipLaunchKernelGGL(k_pmap_trias, dim3((unsigned)nbs), dim3(256), 0, s, tris, nt, np, tmap, cnt + 1);
 }

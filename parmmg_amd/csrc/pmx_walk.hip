@@ -292,7 +292,10 @@ __device__ __forceinline__ void walk_finish(const VolArgs &A, int64_t i, D3 p, b
 }
 
 // ---- k_walk: the reference's walk order ----------------------------------------
-template <int LAYOUT, int S, bool TIES>
+// PM (PMX_RUN_POINTMAP): the start tet is the one resolved from the point's
+// source vertex (A.grid then holds one start per list entry) instead of the
+// hint grid's
+template <int LAYOUT, int S, bool TIES, bool PM = false>
 __global__ __launch_bounds__(256) void k_walk(VolArgs A) {
   const int64_t b = walk_xcd_remap(blockIdx.x, gridDim.x);
   const int64_t j = b * blockDim.x + threadIdx.x;
@@ -301,7 +304,9 @@ __global__ __launch_bounds__(256) void k_walk(VolArgs A) {
   if (j < *A.nlist_dev) {     // the step's count (the grid is sized by an upper bound)
     const int64_t i = A.list[j];
     const D3 p{A.q[3 * i], A.q[3 * i + 1], A.q[3 * i + 2]};
-    int cur = walk_hint(A.grid, A.g, p);
+    int cur;
+    if constexpr (PM) cur = A.grid[j];
+    else cur = walk_hint(A.grid, A.g, p);
     if (A.rec_start) A.start[i] = cur;
     int ring[WALK_RING];
 #pragma unroll
@@ -469,7 +474,8 @@ __device__ __forceinline__ int hint_with_rec(const VolArgs &A, D3 p, TetRec &t) 
 
 // FAR: the compact records have far neighbour fields (VolArgs.far); without
 // them the walk compiles no resolution path
-template <int LAYOUT, int S, bool TIES, bool CW, bool HREC = false, bool FAR = true>
+// PM: as in k_walk
+template <int LAYOUT, int S, bool TIES, bool CW, bool HREC = false, bool FAR = true, bool PM = false>
 __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
   const int64_t b = walk_xcd_remap(blockIdx.x, gridDim.x);
   const int64_t j = b * blockDim.x + threadIdx.x;
@@ -484,7 +490,10 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
     const D3 p{A.q[3 * i], A.q[3 * i + 1], A.q[3 * i + 2]};
     TetRec t;
     int cur;
-    if constexpr (HREC) {
+    if constexpr (PM) {
+      cur = A.grid[j];
+      t = walk_rec<CW>(A, cur, FAR && A.exp == 17);
+    } else if constexpr (HREC) {
       cur = hint_with_rec(A, p, t);
     } else {
       cur = walk_hint(A.grid, A.g, p);
@@ -625,7 +634,26 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
 }
 
 template <int LAYOUT, int S>
-static void launch_walk_t(const VolArgs &a, int64_t nb, hipStream_t s) {
+static void launch_walk_t(const VolArgs &a, int64_t nb, hipStream_t s, bool pointmap) {
+  if (pointmap) {
+    // point-map starts: the same variants, without the measurement switches
+    // of the launch shape; the compact records' far fields always resolvable
+    if (a.ref_walk) {
+      if (a.inline_ties) hipLaunchKernelGGL((k_walk<LAYOUT, S, true, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_walk<LAYOUT, S, false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    } else if (a.wrec && a.exp != 6) {
+      if (a.inline_ties)
+        hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, false, true, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, false, true, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    } else {
+      if (a.inline_ties)
+        hipLaunchKernelGGL((k_walks<LAYOUT, S, true, false, false, false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+      else
+        hipLaunchKernelGGL((k_walks<LAYOUT, S, false, false, false, false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    }
+    return;
+  }
   if (a.ref_walk) {
     if (a.inline_ties) hipLaunchKernelGGL((k_walk<LAYOUT, S, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_walk<LAYOUT, S, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
@@ -652,25 +680,25 @@ static void launch_walk_t(const VolArgs &a, int64_t nb, hipStream_t s) {
   }
 }
 
-void launch_walk(const VolArgs &a, hipStream_t s) {
+void launch_walk(const VolArgs &a, hipStream_t s, bool pointmap) {
   const int64_t nb = (a.nlist + 255) / 256;
   if (nb < 1) return;
   int S = 0;
   const int lay = walk_layout(a.sd, &S);
-  if (lay == LAYOUT_ANI) return launch_walk_t<LAYOUT_ANI, 6>(a, nb, s);
+  if (lay == LAYOUT_ANI) return launch_walk_t<LAYOUT_ANI, 6>(a, nb, s, pointmap);
   if (lay == LAYOUT_ISO) {
     switch (S) {
-      case 1: return launch_walk_t<LAYOUT_ISO, 1>(a, nb, s);
-      case 2: return launch_walk_t<LAYOUT_ISO, 2>(a, nb, s);
-      case 3: return launch_walk_t<LAYOUT_ISO, 3>(a, nb, s);
-      case 4: return launch_walk_t<LAYOUT_ISO, 4>(a, nb, s);
-      case 5: return launch_walk_t<LAYOUT_ISO, 5>(a, nb, s);
-      case 6: return launch_walk_t<LAYOUT_ISO, 6>(a, nb, s);
-      case 7: return launch_walk_t<LAYOUT_ISO, 7>(a, nb, s);
-      default: return launch_walk_t<LAYOUT_ISO, 8>(a, nb, s);
+      case 1: return launch_walk_t<LAYOUT_ISO, 1>(a, nb, s, pointmap);
+      case 2: return launch_walk_t<LAYOUT_ISO, 2>(a, nb, s, pointmap);
+      case 3: return launch_walk_t<LAYOUT_ISO, 3>(a, nb, s, pointmap);
+      case 4: return launch_walk_t<LAYOUT_ISO, 4>(a, nb, s, pointmap);
+      case 5: return launch_walk_t<LAYOUT_ISO, 5>(a, nb, s, pointmap);
+      case 6: return launch_walk_t<LAYOUT_ISO, 6>(a, nb, s, pointmap);
+      case 7: return launch_walk_t<LAYOUT_ISO, 7>(a, nb, s, pointmap);
+      default: return launch_walk_t<LAYOUT_ISO, 8>(a, nb, s, pointmap);
     }
   }
-  launch_walk_t<LAYOUT_GEN, 0>(a, nb, s);
+  launch_walk_t<LAYOUT_GEN, 0>(a, nb, s, pointmap);
 }
 
 // ---- PMX_RUN_SEQUENTIAL_VOLUME: the reference's own walk, replayed in order --

@@ -75,6 +75,8 @@ class Transfer:
     """One device context (one GPU).  ``device`` = rank % ndev in ParMmg terms."""
 
     def __init__(self, device: int = 0):
+        self._peer = None     # second context of interp_metrics_and_fields with sources
+        self.device = device
         self.lib = N.load()
         self.ctx = self.lib.pmx_create(device)
         if not self.ctx:
@@ -85,6 +87,9 @@ class Transfer:
         self.n_new_tets = 0
 
     def close(self):
+        if self._peer is not None:
+            self._peer.close()
+            self._peer = None
         if self.ctx:
             self.lib.pmx_destroy(self.ctx)
             self.ctx = None
@@ -166,14 +171,40 @@ class Transfer:
         # new_mesh_qual(None) sizes its output by them
         self.n_new_tets = int(pv.ne) if pv.tetra_v else 0
 
+    def upload_point_sources(self, src: np.ndarray | None):
+        """Source vertices of the uploaded points (MMG5_Point.src of a ParMmg
+        built with USE_POINTMAP): src[j] = the 1-based background vertex the
+        j-th point descends from (0 / out of range: unset).  Kept until the
+        next upload_points; None forgets them.  Read by run(pointmap=True)."""
+        if src is None:
+            self._chk(self.lib.pmx_upload_point_sources(self.ctx, None, 4), "pmx_upload_point_sources")
+            return
+        a = np.ascontiguousarray(src, np.int32)
+        if a.shape != (self.npts,):
+            raise ValueError("upload_point_sources: one source per uploaded point")
+        # the C view is 1-based like the points view (first = 1)
+        self._chk(self.lib.pmx_upload_point_sources(self.ctx, _shift(a, 4, C.c_int), 4),
+                  "pmx_upload_point_sources")
+
+    def pointmap_stats(self) -> dict:
+        """atomicMin operations the last first-incident-element map build
+        issued (tet pass, tria pass)."""
+        a = (N.i64 * 2)()
+        self._chk(self.lib.pmx_pointmap_stats(self.ctx, a), "pmx_pointmap_stats")
+        return {"atomics_tets": a[0], "atomics_trias": a[1]}
+
     def run(self, hsiz: float = 0.0, timing: bool = False, max_walk: int = 0, hint_stride: int = 0,
-            flags: int = 0, record_starts: bool = False):
+            flags: int = 0, record_starts: bool = False, pointmap: bool = False):
         """One step (asynchronous; device-side failures surface in
         synchronize()/download()).  flags: ``_native.RUN_*``.  record_starts:
         keep every volume point's walk start tet for starts() (diagnostics;
-        the production step does not write it)."""
+        the production step does not write it).  pointmap: every walk starts
+        from its point's source vertex (upload_point_sources) instead of the
+        hint grids."""
         if record_starts:
             flags |= N.RUN_RECORD_STARTS
+        if pointmap:
+            flags |= N.RUN_POINTMAP
         o = N.RunOpts()
         o.hsiz, o.timing, o.max_walk, o.hint_stride, o.flags = hsiz, int(timing), max_walk, hint_stride, flags
         self._chk(self.lib.pmx_run(self.ctx, C.byref(o)), "pmx_run")
@@ -299,10 +330,19 @@ class Transfer:
         ``tags`` (uint16, np+1), ``met`` / ``fields`` (output arrays in Mmg
         layout, written in place), ``hsiz``, optionally ``tets`` (the new
         tets, (ne+1, 4) in Mmg's 1-based layout: the orphan rule and, with
-        PMX_SEQUENTIAL set, the reference's visit order)."""
+        PMX_SEQUENTIAL set, the reference's visit order) and ``src`` (int32,
+        np+1: each new point's source vertex in the old mesh, MMG5_Point.src
+        of a USE_POINTMAP build -- that group's walks start from it)."""
         keep = []
         G = (N.Group * len(groups))()
-        for g, d in zip(G, groups):
+        srcs = (N.PointSources * max(len(groups), 1))()
+        any_src = False
+        for (g, d), ps in zip(zip(G, groups), srcs):
+            if d.get("src") is not None:
+                sa = np.ascontiguousarray(d["src"], np.int32)
+                keep.append(sa)
+                ps.src, ps.stride = _ip(sa), 4
+                any_src = True
             xyz = np.ascontiguousarray(d["xyz"], np.float64)
             tags = np.ascontiguousarray(d["tags"], np.uint16)
             keep += [xyz, tags]
@@ -338,6 +378,15 @@ class Transfer:
         perm = None
         if perm_nod_glob is not None:
             perm = np.ascontiguousarray(perm_nod_glob, np.int32)
+        if any_src:
+            # the seam with sources takes one context per group: alternate
+            # between this one and a second one, as the plain call does
+            if len(groups) > 1 and self._peer is None:
+                self._peer = Transfer(self.device)
+            ctxs = (C.c_void_p * len(groups))(*[self._peer.ctx if (len(groups) > 1 and i & 1) else self.ctx
+                                                for i in range(len(groups))])
+            return self.lib.PMX_interpMetricsAndFields_groups_src(ctxs, len(groups), G, srcs, _ip(perm),
+                                                                  input_met)
         return self.lib.PMX_interpMetricsAndFields(self.ctx, len(groups), G, _ip(perm), input_met)
 
     # ---- statistics -----------------------------------------------------------
