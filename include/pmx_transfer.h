@@ -36,7 +36,8 @@ extern "C" {
 #define PMX_TAG_REQ   4        /* MG_REQ */
 #define PMX_TAG_BDY   16       /* MG_BDY */
 #define PMX_TAG_NUL   16384    /* MG_NUL */
-#define PMX_MAX_SOLS  8        /* metric + fields per group */
+#define PMX_MAX_SOLS  8        /* solutions of one fused step (and of a Medit
+                                  file); further ones: pmx_interp_more */
 
 typedef struct pmx_ctx pmx_ctx;
 
@@ -219,6 +220,17 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *opts);
  * elem/status/steps -- with npts = last - first + 1 of the points view. */
 int pmx_download(pmx_ctx *ctx, const pmx_sol_view *new_sols, int64_t npts_cap, int *elem,
                  int *status, int *steps);
+/* After a pmx_run on ctx: nsol (>= 1, any number) further solutions of the
+ * uploaded background, interpolated onto the points that step located, from
+ * that step's elements.  old_sols[k].m: np+1 rows in Mmg layout; new_sols /
+ * npts_cap as in pmx_download (rows the reference leaves alone are not
+ * written).  Batched internally by PMX_MAX_SOLS.  0 + pmx_last_error: no step
+ * yet, points or background uploaded since the step, null or mismatched views.
+ * No walk is run: a volume point's barycentrics are recomputed from its
+ * element and status, a surface point's were kept by the step.  The step's own
+ * results (pmx_download) are not changed. */
+int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_sols,
+                    const pmx_sol_view *new_sols, int64_t npts_cap);
 /* Per-point start element used by the device walk (debug/parity).  Volume
  * points' starts are recorded only by a pmx_run with PMX_RUN_RECORD_STARTS;
  * surface points' always.  cap: ints in start (>= npts). */
@@ -298,7 +310,9 @@ double pmx_topo_ms(pmx_ctx *ctx);
 /* Kernel timing of the last pmx_run with opts.timing != 0, in ms:
  * which = 0 hint build, 1 volume locate+interp, 2 surface locate+interp,
  * 3 exhaustive fallback, 4 total, 5 derived data, 6 the first-incident-element
- * maps of a PMX_RUN_POINTMAP step (0 when the step built none). */
+ * maps of a PMX_RUN_POINTMAP step (0 when the step built none).
+ * which = 7: the batch kernels of the last pmx_interp_more, summed over its
+ * batches (always recorded; -1 before the first call). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);

@@ -120,12 +120,13 @@ int PMMG_copyMetricsAndFields_point(MMG5_pMesh mesh, MMG5_pMesh oldMesh, MMG5_pS
                                     MMG5_pSol oldMet, MMG5_pSol field, MMG5_pSol oldField,
                                     int *permNodGlob, uint8_t inputMet) {
   pmx_group g;
-  pmx_sol_view m, om, fl[PMX_MAX_SOLS], ofl[PMX_MAX_SOLS];
-  int j;
-  if (mesh->nsols > PMX_MAX_SOLS) {
-    fprintf(stderr, "  ## Error: %s: more than %d solution fields.\n", __func__, PMX_MAX_SOLS);
-    return 0;
-  }
+  pmx_sol_view m, om, *fl = NULL, *ofl;
+  const int nfl = mesh->nsols > 0 ? mesh->nsols : 0;
+  int j, ier;
+  /* any number of fields: the views are sized by mesh->nsols (new | old;
+   * none allocated without fields) */
+  PMMG_CALLOC(mesh, fl, 2 * nfl, pmx_sol_view, "pmx sols", return 0);
+  ofl = fl ? fl + nfl : NULL;
   memset(&g, 0, sizeof g);
   view_mesh(oldMesh, &g.old_mesh);
   if (met) view_sol(met, &m);
@@ -134,9 +135,10 @@ int PMMG_copyMetricsAndFields_point(MMG5_pMesh mesh, MMG5_pMesh oldMesh, MMG5_pS
   g.old_met = oldMet && oldMet->m ? &om : NULL;
   for (j = 0; j < mesh->nsols; j++) { view_sol(&field[j], &fl[j]); view_sol(&oldField[j], &ofl[j]); }
   g.fields = fl; g.old_fields = ofl; g.nsols = mesh->nsols; g.hsiz = mesh->info.hsiz;
-  if (!PMX_copyMetricsAndFields_point(PMMG_pmx, &g, &oldMesh->point[0].tag, sizeof(MMG5_Point),
-                                      permNodGlob, oldMesh->info.renum, inputMet))
-    return pmx_fail(PMMG_pmx, __func__);
+  ier = PMX_copyMetricsAndFields_point(PMMG_pmx, &g, &oldMesh->point[0].tag, sizeof(MMG5_Point),
+                                       permNodGlob, oldMesh->info.renum, inputMet);
+  PMMG_DEL_MEM(mesh, fl, pmx_sol_view, "pmx sols");
+  if (!ier) return pmx_fail(PMMG_pmx, __func__);
   return 1;
 }
 
@@ -144,9 +146,9 @@ int PMMG_copyMetricsAndFields_point(MMG5_pMesh mesh, MMG5_pMesh oldMesh, MMG5_pS
  * context (group g+1's upload overlaps group g's step); the contexts keep the
  * groups' new meshes and results for PMMG_tetraQual */
 int PMMG_interpMetricsAndFields(PMMG_pParMesh parmesh, int *permNodGlob) {
-  int ngrp = parmesh->ngrp, igrp, j, ier;
+  int ngrp = parmesh->ngrp, igrp, j, ier, nsv = 0;
   pmx_group *g;
-  pmx_sol_view *sv;
+  pmx_sol_view *sv, *svg;
 #ifdef USE_POINTMAP
   /* Mmg's point map: every new point's source vertex in the old mesh
    * (MMG5_Point.src, seeded at src/libparmmg1.c:667-670) starts its walk, as
@@ -157,27 +159,27 @@ int PMMG_interpMetricsAndFields(PMMG_pParMesh parmesh, int *permNodGlob) {
   if (!ctxs) return 0;
   for (igrp = 0; igrp < PMMG_pmx_ngrp; igrp++) PMMG_pmx_state[igrp].valid = 0;
   PMMG_CALLOC(parmesh, g, ngrp, pmx_group, "pmx groups", return 0);
-  PMMG_CALLOC(parmesh, sv, ngrp * 2 * (PMX_MAX_SOLS + 1), pmx_sol_view, "pmx sols",
+  /* per group: new metric | old metric | new fields | old fields, any number
+   * of fields (the library interpolates those beyond the fused step's
+   * PMX_MAX_SOLS in batches, from the step's elements) */
+  for (igrp = 0; igrp < ngrp; igrp++) {
+    const int ns = parmesh->listgrp[igrp].mesh->nsols;
+    nsv += 2 * ((ns > 0 ? ns : 0) + 1);
+  }
+  PMMG_CALLOC(parmesh, sv, nsv, pmx_sol_view, "pmx sols",
               PMMG_DEL_MEM(parmesh, g, pmx_group, "pmx groups"); return 0);
 #ifdef USE_POINTMAP
   PMMG_CALLOC(parmesh, ps, ngrp, pmx_point_sources, "pmx sources",
               PMMG_DEL_MEM(parmesh, sv, pmx_sol_view, "pmx sols");
               PMMG_DEL_MEM(parmesh, g, pmx_group, "pmx groups"); return 0);
 #endif
+  svg = sv;
   for (igrp = 0; igrp < ngrp; igrp++) {
     PMMG_pGrp G = &parmesh->listgrp[igrp], O = &parmesh->old_listgrp[igrp];
     MMG5_pMesh mesh = G->mesh;
-    pmx_sol_view *met = sv + igrp * 2 * (PMX_MAX_SOLS + 1), *omet = met + 1,
-                 *fl = met + 2, *ofl = fl + PMX_MAX_SOLS;
-    if (mesh->nsols > PMX_MAX_SOLS) {
-      fprintf(stderr, "  ## Error: %s: more than %d solution fields.\n", __func__, PMX_MAX_SOLS);
-#ifdef USE_POINTMAP
-      PMMG_DEL_MEM(parmesh, ps, pmx_point_sources, "pmx sources");
-#endif
-      PMMG_DEL_MEM(parmesh, sv, pmx_sol_view, "pmx sols");
-      PMMG_DEL_MEM(parmesh, g, pmx_group, "pmx groups");
-      return 0;
-    }
+    const int nfl = mesh->nsols > 0 ? mesh->nsols : 0;
+    pmx_sol_view *met = svg, *omet = met + 1, *fl = met + 2, *ofl = fl + nfl;
+    svg += 2 * (nfl + 1);
     /* the new mesh: its points (located) and tets (only the vertices of valid
      * tets are visited, src/interpmesh_pmmg.c:535-541) */
     view_mesh(mesh, &g[igrp].mesh);

@@ -161,6 +161,7 @@ SIGNATURES = {
     "pmx_pointmap_stats": (C.c_int, [C.c_void_p, C.POINTER(i64)]),
     "pmx_run": (C.c_int, [C.c_void_p, C.POINTER(RunOpts)]),
     "pmx_download": (C.c_int, [C.c_void_p, C.POINTER(SolView), i64, iptr, iptr, iptr]),
+    "pmx_interp_more": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SolView), C.POINTER(SolView), i64]),
     "pmx_download_starts": (C.c_int, [C.c_void_p, iptr, i64]),
     "pmx_download_border": (C.c_int, [C.c_void_p, iptr, iptr, i64]),
     "pmx_step_ready": (C.c_int, [C.c_void_p]),

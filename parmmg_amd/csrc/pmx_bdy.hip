@@ -39,6 +39,8 @@ struct BdyArgs {
   double *out;
   uint8_t *wmask;
   int *elem, *status, *steps, *start, *edge, *vertex;
+  Pt4 *bphi;           // (non-null, nlist entries) per entry of `list`: the 3 barycentrics the point's fields were
+                       // interpolated with, in the tria's vertex order (pmx_interp_more)
   int *stuck_list;     // bdy exhaustive list
   unsigned *stuck_count;
   int *ovf_list;       // private-list overflow
@@ -368,8 +370,13 @@ __device__ bool in_cone(const BdyArgs &A, St &s, int k, int iloc, D3 p, int base
 
 // ---- interpolation on a boundary triangle --------------------------------
 
+// keep (may be null): where the barycentrics, in the tria's vertex order, are
+// kept for pmx_interp_more -- the walk's barycoord array as PMMG_barycoord_get
+// orders it is not a function of (tria, point) alone: a shadow-wedge hit
+// rewrites it, the exhaustive not-found branch evaluates it on another tria's
+// geometry
 __device__ void interp_tria(const BdyArgs &A, int k, const Bary &b, int edge, int vtx,
-                            double *out, unsigned &wm) {
+                            double *out, unsigned &wm, Pt4 *keep = nullptr) {
   TriRec t = A.tris[k];
   int v[3] = {t.v[0], t.v[1], t.v[2]};
   double phi[3];
@@ -381,6 +388,7 @@ __device__ void interp_tria(const BdyArgs &A, int k, const Bary &b, int edge, in
     if (id == 1) phi[1] = val;
     if (id == 2) phi[2] = val;
   }
+  if (keep) *keep = Pt4{phi[0], phi[1], phi[2], 0.0};
   const SolDesc &sd = A.sd;
   for (int s = 0; s < sd.nsol; ++s) {
     if (s == sd.imet && sd.metric_const) continue;
@@ -496,15 +504,32 @@ __device__ int walk_bdy(const BdyArgs &A, St &s, D3 p, int start, int base, int 
   return 2;
 }
 
+// position of point i in the surface list (ascending: the compaction keeps
+// the input order); for the finishers that know the point only (overflow
+// pass, exhaustive scan, sequential replay -- a few points of a step)
+__device__ int64_t bdy_slot(const BdyArgs &A, int64_t i) {
+  int64_t lo = 0, hi = *A.nlist_dev;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (A.list[mid] < i) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// slot: the point's position in the surface list (< 0: looked up)
 __device__ void finish_bdy(const BdyArgs &A, int64_t i, int k, const Bary &b, int edge, int vtx,
-                           int status, int step) {
+                           int status, int step, int64_t slot = -1) {
   A.elem[i] = k;
   A.status[i] = status;
   A.steps[i] = step;
   A.edge[i] = edge;
   A.vertex[i] = vtx;
+  if (slot < 0) slot = bdy_slot(A, i);
+  // (only the list's own entry: a point that is not in the surface list keeps nothing)
+  const bool mine = slot < *A.nlist_dev && slot < A.nlist && A.list[slot] == i;
   unsigned wm = 0;
-  interp_tria(A, k, b, edge, vtx, A.out + i * A.sd.S, wm);
+  interp_tria(A, k, b, edge, vtx, A.out + i * A.sd.S, wm, mine ? A.bphi + slot : nullptr);
   A.wmask[i] = (uint8_t)(A.wmask[i] | wm);
 }
 
@@ -530,7 +555,7 @@ __global__ __launch_bounds__(256) void k_locate_bdy(BdyArgs A) {
     int r = walk_bdy(A, s, p, start, base, k, b, edge, vtx, step, wedged);
     if (A.seq_w) A.seq_w[i] = wedged ? 1 : 0;
     if (r == 1) {
-      finish_bdy(A, i, k, b, edge, vtx, 1, step);
+      finish_bdy(A, i, k, b, edge, vtx, 1, step, j);
       s_cnt = 1; s_sum = (unsigned)step; s_max = (unsigned)step; s_min = (unsigned)step;
     } else if (r == 2) {
       unsigned slot = atomicAdd(A.stuck_count, 1u);
@@ -1088,6 +1113,7 @@ static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap = false) {
   B.hausd = c->hausd; B.grid = c->d_tgrid; B.g = c->tgd;
   B.out = c->d_out.p; B.wmask = c->d_wmask.p; B.elem = c->d_elem.p; B.status = c->d_status.p;
   B.steps = c->d_steps.p; B.start = c->d_start.p; B.edge = c->d_edge.p; B.vertex = c->d_vertex.p;
+  B.bphi = c->d_bphi.p;
   B.stuck_list = c->d_blist.p; B.stuck_count = c->d_counts.p + 1;
   B.ovf_list = c->d_olist.p; B.ovf_count = c->d_counts.p + 2;
   B.list = c->d_bdylist.p; B.nlist = c->nq_bdy_ub; B.nlist_dev = c->d_nsel.p + 1; B.wstats = c->d_bstat.p;
@@ -1125,6 +1151,7 @@ bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
     if (hipMalloc((void **)&d_olist.p, sizeof(int) * (size_t)std::max<int64_t>(nq, 1)) != hipSuccess) { err = "hipMalloc olist"; return false; }
     d_olist.cap = (size_t)nq;
   }
+  if (!pmx_dgrow(this, d_bphi, (size_t)std::max<int64_t>(nq_bdy_ub, 1))) return false;
   if (!d_ows.p) {
     if (hipMalloc((void **)&d_ows.p, sizeof(int) * (size_t)OVF_THREADS * 3 * OVF_CAP) != hipSuccess) { err = "hipMalloc ows"; return false; }
     d_ows.cap = (size_t)OVF_THREADS * 3 * OVF_CAP;

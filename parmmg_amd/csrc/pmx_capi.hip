@@ -499,6 +499,7 @@ void pmx_destroy(pmx_ctx *ctx) {
   if (ctx->up) hipStreamSynchronize(ctx->up);
   ctx->free_all();
   for (auto &e : ctx->events) hipEventDestroy(e);
+  for (auto &e : ctx->more_ev) hipEventDestroy(e);
   if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_fork2) hipEventDestroy(ctx->ev_fork2);
   if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
@@ -1444,6 +1445,7 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
   if (marks) ctx->orph_marks = true;
   ctx->out_S = S;
   ctx->out_n = n;
+  ctx->located = any_interp;
   if ((opts.flags & PMX_RUN_EAGER_DOWNLOAD) && !ctx->eager_download()) return 0;
   if (ctx->tets_pending && !ctx->pack_new_tets()) return 0;
   ctx->ran = true;
@@ -1841,6 +1843,7 @@ int pmx_timing_reset(pmx_ctx *ctx) {
 }
 
 double pmx_kernel_ms(pmx_ctx *ctx, int which) {
+  if (ctx && which == 7) return pmx_more_kernel_ms(ctx);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
@@ -2178,6 +2181,7 @@ void pmx_ctx::free_all() {
   dfree(d_steps); dfree(d_start); dfree(d_edge); dfree(d_vertex); dfree(d_list); dfree(d_found);
   dfree(d_bestk); dfree(d_best); dfree(d_ties); dfree(d_counts); dfree(d_vollist); dfree(d_bdylist);
   dfree(d_vstat); dfree(d_bstat); dfree(d_hrec);
+  dfree(d_bphi); dfree(d_msol); dfree(d_mout); dfree(d_mwm);
   dfree(d_qsrc); dfree(d_pstart); dfree(d_pmap); dfree(d_pmcnt);
   have_src = have_pmap = false;
   dfree(d_sqkey); dfree(d_sqidx); dfree(d_sqint); dfree(d_sqtf); dfree(d_sqpf); dfree(d_sqtv); dfree(d_sqows); dfree(d_sqval);

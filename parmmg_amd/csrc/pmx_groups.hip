@@ -66,12 +66,23 @@ static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_grou
     int ns = 0;
     int64_t cap = 0;                       // rows the caller's arrays hold from `first` on
     pmx_sol_view news[PMX_MAX_SOLS];
+    // the fields beyond the fused step's PMX_MAX_SOLS: interpolated from the
+    // step's elements (pmx_interp_more) when the group is finished
+    const pmx_sol_view *more_old = nullptr;
+    std::vector<pmx_sol_view> more_new;
   };
   std::vector<Pending> pend((size_t)std::max(ngrp, 1));
   auto finish = [&](int g) {
     if (!pend[g].on) return;
     pend[g].on = false;
-    if (!pmx_download(ctxs[g], pend[g].news, pend[g].cap, nullptr, nullptr, nullptr)) fail(ctxs[g]);
+    if (!pmx_download(ctxs[g], pend[g].news, pend[g].cap, nullptr, nullptr, nullptr)) { fail(ctxs[g]); return; }
+    // on the group's context, which still holds its step (it takes its next
+    // group only after this): like the download, after the later groups'
+    // uploads and steps are enqueued
+    if (!pend[g].more_new.empty() &&
+        !pmx_interp_more(ctxs[g], (int)pend[g].more_new.size(), pend[g].more_old, pend[g].more_new.data(),
+                         pend[g].cap))
+      fail(ctxs[g]);
   };
   for (int g = 0; g < ngrp; g++) {
     pmx_ctx *X = ctxs[g];
@@ -84,7 +95,7 @@ static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_grou
     const bool cst = (inputMet == 1) && G.hsiz > 0.0 && G.met && G.met->m;
     const bool ismet = (inputMet == 1) && !(G.hsiz > 0.0) && G.met && G.met->m && G.old_met &&
                        G.old_met->m;
-    if (G.nsols < 0 || G.nsols > PMX_MAX_SOLS || (G.nsols > 0 && (!G.fields || !G.old_fields))) {
+    if (G.nsols < 0 || (G.nsols > 0 && (!G.fields || !G.old_fields))) {
       X->err = "PMX_interpMetricsAndFields: bad field list";
       fail(X);
       continue;
@@ -109,14 +120,15 @@ static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_grou
       P.news[ns] = *G.met;
       imet = ns++;
     }
-    bool bad = false;
-    for (int j = 0; j < G.nsols; j++) {
-      if (ns >= PMX_MAX_SOLS) { bad = true; break; }
-      olds[ns] = G.old_fields[j];
-      P.news[ns] = G.fields[j];
+    // the metric and the first fields, PMX_MAX_SOLS solutions in all, go
+    // through the fused step; the fields from `jmore` on through
+    // pmx_interp_more, from the step's elements
+    int jmore = 0;
+    for (; jmore < G.nsols && ns < PMX_MAX_SOLS; jmore++) {
+      olds[ns] = G.old_fields[jmore];
+      P.news[ns] = G.fields[jmore];
       ns++;
     }
-    if (bad) { X->err = "PMX_interpMetricsAndFields: too many solution fields"; fail(X); continue; }
     if (!pmx_upload_background(X, &G.old_mesh, ns, olds, imet)) { fail(X); continue; }
     // the background upload invalidated nothing of the points; run the step
     pmx_run_opts o{};
@@ -144,6 +156,10 @@ static int interp_groups(pmx_ctx *ectx, pmx_ctx *const *ctxs, int ngrp, pmx_grou
     // given, else the points view's last)
     P.cap = (G.mesh.np > 0 ? G.mesh.np : G.points.last) + 1 - G.points.first;
     P.on = true;
+    P.more_old = G.old_fields + jmore;
+    P.more_new.assign(G.fields + jmore, G.fields + G.nsols);
+    for (pmx_sol_view &v : P.more_new)
+      if (v.m) v.m += (int64_t)v.size * G.points.first;
   }
   for (int g = 0; g < ngrp; g++) finish(g);
   if (!ier) ectx->err = first_err;
@@ -214,7 +230,7 @@ extern "C" int PMX_copyMetricsAndFields_point(pmx_ctx *ctx, pmx_group *G, const 
     olds.push_back(G->old_met);
     news.push_back(G->met);
   }
-  if (G->nsols < 0 || G->nsols > PMX_MAX_SOLS || (G->nsols > 0 && (!G->fields || !G->old_fields)))
+  if (G->nsols < 0 || (G->nsols > 0 && (!G->fields || !G->old_fields)))
     return fail("PMX_copyMetricsAndFields_point: bad field list");
   for (int j = 0; j < G->nsols; j++) {
     olds.push_back(&G->old_fields[j]);

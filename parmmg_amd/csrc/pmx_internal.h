@@ -116,6 +116,17 @@ struct pmx_ctx {
   DevBuf<unsigned long long> d_best;
   DevBuf<unsigned> d_counts;            // step counters, see pmx_kernels.h
   DevBuf<int> d_vollist, d_bdylist;     // compacted point lists per path
+  // per entry of d_bdylist (nq_bdy_ub of them): the barycentrics the located
+  // surface point's fields were interpolated with
+  DevBuf<Pt4> d_bphi;
+  // pmx_interp_more (pmx_more.hip): the step located points (it had something
+  // to interpolate), a batch's background rows, output rows and write masks
+  // (reused across batches and calls), the batch kernels' events of the last call
+  bool located = false;
+  DevBuf<double> d_msol, d_mout;
+  DevBuf<uint8_t> d_mwm;
+  std::vector<hipEvent_t> more_ev;
+  int more_ev_used = 0;
   DevBuf<double> d_qxyz;                // new points as uploaded (dense xyz)
   DevBuf<uint8_t> d_qmark;              // orphan marks (points of valid new tets), uploaded when needed
   DevBuf<int> d_nsel;                   // compaction counts: volume, surface
@@ -307,5 +318,7 @@ void pmx_par_for(int64_t lo, int64_t hi, const std::function<void(int64_t, int64
 bool pmx_ctx_build_adja_device(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t np, int *dadja,
                                hipStream_t s, unsigned *h_nbad);
 extern "C" int pmx_timing_reset(pmx_ctx *ctx);
+// pmx_kernel_ms(ctx, 7): the batch kernels of the last pmx_interp_more (pmx_more.hip)
+double pmx_more_kernel_ms(pmx_ctx *ctx);
 // error of a call made without a context (pmx_last_error(NULL), per thread)
 void pmx_set_noctx_error(const char *msg);

@@ -118,14 +118,7 @@ __device__ __forceinline__ D3 dsel(bool c, D3 a, D3 b) {
   return D3{c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z};
 }
 
-// ---- layout-specialised interpolation --------------------------------------
-//
-// LAYOUT_ANI: one solution, the 6-component metric (C2): interp4bar_ani.
-// LAYOUT_ISO: every solution of size 1 or 3 and no constant metric: a row of
-//             S doubles per vertex, out_j = ((0 + phi0 a0j) + phi1 a1j) ...
-//             (interp4bar_iso, src/interpmesh_pmmg.c:206-230, order kept).
-// LAYOUT_GEN: interp_bar<4> of pmx_device.h.
-enum { LAYOUT_GEN = 0, LAYOUT_ANI = 1, LAYOUT_ISO = 2 };
+// ---- layout-specialised interpolation: interp_layout (pmx_device.h) ---------
 
 // layout of the solutions for the walk kernel
 static int walk_layout(const SolDesc &sd, int *S) {
@@ -134,63 +127,6 @@ static int walk_layout(const SolDesc &sd, int *S) {
   bool iso = !sd.metric_const && sd.S >= 1 && sd.S <= 8;
   for (int s = 0; s < sd.nsol; s++) iso = iso && sd.size[s] != 6;
   return iso ? LAYOUT_ISO : LAYOUT_GEN;
-}
-
-template <int LAYOUT, int S>
-__device__ __forceinline__ unsigned interp_layout(const double *__restrict__ sol, const SolDesc &sd,
-                                                  const int *v, const double *phi,
-                                                  double *__restrict__ out) {
-  if constexpr (LAYOUT == LAYOUT_ANI) {
-    double mint[6], r[6];
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const double2 *m = reinterpret_cast<const double2 *>(sol + (int64_t)v[i] * 6);
-      double2 a = m[0], b = m[1], c = m[2];
-      double mm[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-      double mi[6];
-      ok = ok && invmat(mm, mi);
-#pragma unroll
-      for (int j = 0; j < 6; j++) mint[j] = (i == 0) ? phi[i] * mi[j] : mint[j] + phi[i] * mi[j];
-    }
-    // a failed inversion leaves the output untouched (src/interpmesh_pmmg.c:258-267)
-    if (!ok || !invmat(mint, r)) return 0u;
-    double2 *o = reinterpret_cast<double2 *>(out);
-    o[0] = make_double2(r[0], r[1]);
-    o[1] = make_double2(r[2], r[3]);
-    o[2] = make_double2(r[4], r[5]);
-    return 1u;
-  } else if constexpr (LAYOUT == LAYOUT_ISO) {
-    double acc[S];
-#pragma unroll
-    for (int j = 0; j < S; j++) acc[j] = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const double *row = sol + (int64_t)v[i] * S;
-      if constexpr ((S & 1) == 0) {
-        // even stride: rows are 16-B aligned, 16-B loads
-#pragma unroll
-        for (int j = 0; j < S; j += 2) {
-          const double2 d = *reinterpret_cast<const double2 *>(row + j);
-          acc[j] += phi[i] * d.x;
-          acc[j + 1] += phi[i] * d.y;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < S; j++) acc[j] += phi[i] * row[j];
-      }
-    }
-    if constexpr ((S & 1) == 0) {
-#pragma unroll
-      for (int j = 0; j < S; j += 2) *reinterpret_cast<double2 *>(out + j) = make_double2(acc[j], acc[j + 1]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < S; j++) out[j] = acc[j];
-    }
-    return (1u << sd.nsol) - 1u;
-  } else {
-    return interp_bar<4>(sol, sd, v, phi, out);
-  }
 }
 
 // Near-face cases of the canonical tie rule resolved in place (canonical_tet,

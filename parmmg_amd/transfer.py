@@ -83,6 +83,7 @@ class Transfer:
             raise RuntimeError("pmx_create failed (no HIP device visible)")
         self._keep = []
         self.sizes: list[int] = []
+        self.bg_np = 0        # vertices of the uploaded background
         self.npts = 0
         self.n_new_tets = 0
 
@@ -132,6 +133,7 @@ class Transfer:
         self._chk(self.lib.pmx_upload_background(self.ctx, C.byref(mv), len(arr), views,
                                                  imet if arr else -1), "pmx_upload_background")
         self.sizes = [v.size for v in views[: len(arr)]]
+        self.bg_np = m.np
 
     def copy_required(self, perm: np.ndarray | None = None, copy_metric: bool = True):
         """pmx_copy_required: frozen (MG_REQ) background points' values into the
@@ -242,6 +244,35 @@ class Transfer:
             self._chk(self.lib.pmx_download(self.ctx, views, n, _ip(elem), _ip(status), _ip(steps)),
                       "pmx_download")
         return Result(outs, elem, status, steps)
+
+    def interp_more(self, sols: list[np.ndarray], init: list[np.ndarray] | None = None) -> list[np.ndarray]:
+        """pmx_interp_more: further solutions of the uploaded background
+        ((np+1, size) arrays in Mmg layout, any number of them) onto the points
+        the last step located, from that step's elements -- no second walk.
+        Returns one (npts, size) array per solution; ``init`` as in
+        :meth:`download` (values kept where the reference writes nothing)."""
+        arr = [np.ascontiguousarray(s, np.float64) for s in sols]
+        if not arr:
+            raise ValueError("interp_more: at least one solution")
+        arr = [a.reshape(-1, 1) if a.ndim == 1 else a for a in arr]
+        for a in arr:
+            # (no background yet: the library refuses the call before it reads a row)
+            if a.ndim != 2 or (self.bg_np > 0 and a.shape[0] != self.bg_np + 1):
+                raise ValueError(f"interp_more: an old field has {a.shape[0]} rows, the uploaded background "
+                                 f"has {self.bg_np} vertices (np + 1 = {self.bg_np + 1} rows expected)")
+        n = self.npts
+        outs = []
+        for i, a in enumerate(arr):
+            sz = a.shape[1]
+            outs.append(np.array(init[i], np.float64, copy=True).reshape(n, sz) if init is not None
+                        else np.full((n, sz), np.nan))
+        olds = (N.SolView * len(arr))()
+        news = (N.SolView * len(arr))()
+        for i, (a, o) in enumerate(zip(arr, outs)):
+            olds[i].size, olds[i].m = a.shape[1], _dp(a)
+            news[i].size, news[i].m = a.shape[1], _dp(o)
+        self._chk(self.lib.pmx_interp_more(self.ctx, len(arr), olds, news, n), "pmx_interp_more")
+        return outs
 
     def starts(self) -> np.ndarray:
         s = np.zeros(self.npts, np.int32)
@@ -378,6 +409,7 @@ class Transfer:
         perm = None
         if perm_nod_glob is not None:
             perm = np.ascontiguousarray(perm_nod_glob, np.int32)
+        self.bg_np = 0                       # the contexts' backgrounds become the groups'
         if any_src:
             # the seam with sources takes one context per group: alternate
             # between this one and a second one, as the plain call does
@@ -521,6 +553,7 @@ class Transfer:
             views[i].m = _dp(a)                 # pmx_download's layout: entry 0 = point 1
         self._chk(self.lib.pmx_promote_background(self.ctx, C.byref(mv), len(arr), views),
                   "pmx_promote_background")
+        self.bg_np = self.npts              # the promoted points are the background's vertices
         self.npts = 0
 
     def new_mesh_qual(self, tets: np.ndarray | None, opt: int = N.INQUA, dev_ptr: int = 0,
