@@ -16,6 +16,8 @@
  *       def src/quality_pmmg.c:156-346,591-733)
  *                                          -> pmx_tetra_qual / pmx_qualhisto /
  *                                             pmx_prilen
+ *   PMMG_graph_meshElts2metis / PMMG_computeWgt (src/metis_pmmg.c:746-823,
+ *       280-301)                           -> pmx_metis_graph / pmx_face_weights
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -312,7 +314,10 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * 3 exhaustive fallback, 4 total, 5 derived data, 6 the first-incident-element
  * maps of a PMX_RUN_POINTMAP step (0 when the step built none).
  * which = 7: the batch kernels of the last pmx_interp_more, summed over its
- * batches (always recorded; -1 before the first call). */
+ * batches (always recorded; -1 before the first call).
+ * which = 8: the device time of the last pmx_metis_graph, summed over its
+ * kernels; 9 / 10 / 11 its count, scan and fill alone (-1 before the first
+ * call). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -570,6 +575,38 @@ int pmx_upload_surface(pmx_ctx *ctx, const pmx_surface_view *sv);
  * (refused without).  Surface edges use pmx_upload_surface's data. */
 int pmx_prilen_device(pmx_ctx *ctx, int metRidTyp, const pmx_par_edges *par, void *dev_result);
 int pmx_prilen(pmx_ctx *ctx, int metRidTyp, const pmx_par_edges *par, pmx_len_stats *st);
+
+/* PMMG_graph_meshElts2metis (src/metis_pmmg.c:746-823) of the uploaded group:
+ * the tets as Metis nodes.  xadj[0] = 0, xadj[k] = xadj[k-1] + the interior
+ * faces of tet k; entries in (k, f) ascending order, adjncy[c] = jel - 1;
+ * adjwgt[c] = max((int)PMMG_computeWgt(mesh, met, pt, f), 1) (:280-301): with
+ * a metric min(1/exp(28 res/3), 1000000), res the sum over the face's edges
+ * ia = MMG5_iarf[f][0..2] of (len <= 1 ? len - 1 : 1/len - 1), len =
+ * MMG5_lenedg(mesh, met, ia, pt); without a metric 1000000.  The lengths are
+ * pmx_prilen's: metRidTyp 0 or 1 for a size-1 metric (MMG5_lenedg_iso); a
+ * size-6 metric takes MMG5_lenedg33_ani for 0 and MMG5_lenedg_ani for 1
+ * (needs the point tags, refused without); tensor lengths of xTetra boundary
+ * edges run along the surface (pmx_upload_surface).  MMG5_iarf, the lenedg
+ * dispatch and the surface lengths are restated from Mmg, unpinned; exp is
+ * the device library's, so a weight within an ulp of an integer may differ
+ * by 1 from a glibc host's.
+ * xadj: ne+1 ints.  adjncy / adjwgt: cap ints each (4*ne always suffices);
+ * adjwgt NULL = no weights (the reference's *adjwgt == NULL: distribution
+ * time and the last iteration).  adjncy NULL = count only (xadj and *nadjncy).
+ * *nadjncy is set whenever the count ran.  Outputs are int32_t, the idx_t of
+ * a default Metis build.  Returns 0 (pmx_last_error): no group uploaded,
+ * 4*ne >= 2^31, a deleted tet (v[0] <= 0: the reference wants a packed mesh),
+ * nadjncy > cap (*nadjncy set, no array written, the fill never launched),
+ * metRidTyp = 1 with a tensor metric and no tags. */
+int pmx_metis_graph(pmx_ctx *ctx, int metRidTyp, int32_t *xadj, int32_t *adjncy, int32_t *adjwgt,
+                    int64_t cap, int64_t *nadjncy);
+/* PMMG_computeWgt as a double for n listed faces of the uploaded group:
+ * face[i] = 12*ie + 3*ifac (+ iloc, ignored), the encoding of
+ * face2int_face_comm_index1 -- the interface-face weights of the group graph
+ * (src/metis_pmmg.c:959) and PMMG_computeWgt_mesh (:242-266).  Returns 0 when
+ * a face[i] is outside 12 .. 12*ne+11 or belongs to a deleted tet, and for
+ * pmx_metis_graph's refusals. */
+int pmx_face_weights(pmx_ctx *ctx, int metRidTyp, int64_t n, const int *face, double *wgt);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

@@ -14,6 +14,7 @@ i64 = C.c_int64
 dptr = C.POINTER(C.c_double)
 iptr = C.POINTER(C.c_int)
 u16ptr = C.POINTER(C.c_uint16)
+i32ptr = C.POINTER(C.c_int32)
 
 
 class MeshView(C.Structure):
@@ -196,6 +197,8 @@ SIGNATURES = {
     "pmx_qualhisto": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(QualStats)]),
     "pmx_prilen_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ParEdges), C.c_void_p]),
     "pmx_prilen": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ParEdges), C.POINTER(LenStats)]),
+    "pmx_metis_graph": (C.c_int, [C.c_void_p, C.c_int, i32ptr, i32ptr, i32ptr, i64, C.POINTER(i64)]),
+    "pmx_face_weights": (C.c_int, [C.c_void_p, C.c_int, i64, iptr, dptr]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

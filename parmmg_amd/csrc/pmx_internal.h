@@ -180,6 +180,17 @@ struct pmx_ctx {
   DevBuf<unsigned> d_pbcnt, d_pboff;
   DevBuf<int4> d_pbrec;
   DevBuf<char> d_pbtmp;
+  // Metis element graph (pmx_metis_graph / pmx_face_weights): degrees (slot 0
+  // = 0, so that their inclusive sum is xadj), xadj, adjncy, adjwgt, the
+  // deleted-tet flag, cub scratch; the face list and its weights; the events
+  // around the count, the scan and the fill of the last call (graph_ev_n of
+  // them recorded: 0 none, 3 count + scan, 5 with a fill)
+  DevBuf<int> d_gdeg, d_gxadj, d_gadj, d_gwgt, d_gface;
+  DevBuf<unsigned> d_gflag;
+  DevBuf<char> d_gtmp;
+  DevBuf<double> d_gfw;
+  std::vector<hipEvent_t> graph_ev;
+  int graph_ev_n = 0;
   int64_t stat_np = -1;                 // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
@@ -320,5 +331,8 @@ bool pmx_ctx_build_adja_device(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t
 extern "C" int pmx_timing_reset(pmx_ctx *ctx);
 // pmx_kernel_ms(ctx, 7): the batch kernels of the last pmx_interp_more (pmx_more.hip)
 double pmx_more_kernel_ms(pmx_ctx *ctx);
+// pmx_kernel_ms(ctx, 8..11): the last pmx_metis_graph -- its kernels summed,
+// the count, the scan, the fill (pmx_stats.hip)
+double pmx_graph_kernel_ms(pmx_ctx *ctx, int which);
 // error of a call made without a context (pmx_last_error(NULL), per thread)
 void pmx_set_noctx_error(const char *msg);

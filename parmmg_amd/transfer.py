@@ -10,6 +10,8 @@ Names and argument meaning follow the reference:
 * :meth:`Transfer.tetra_qual`, :meth:`Transfer.qualhisto`,
   :meth:`Transfer.prilen` -- ``PMMG_tetraQual`` / ``PMMG_qualhisto`` /
   ``PMMG_prilen`` (src/quality_pmmg.c).
+* :meth:`Transfer.metis_graph`, :meth:`Transfer.face_weights` --
+  ``PMMG_graph_meshElts2metis`` / ``PMMG_computeWgt`` (src/metis_pmmg.c).
 
 Errors follow the reference's 1/0 convention at the C ABI and surface here as
 ``RuntimeError`` with ``pmx_last_error``.  Everything runs on the GPU; there is
@@ -84,6 +86,7 @@ class Transfer:
         self._keep = []
         self.sizes: list[int] = []
         self.bg_np = 0        # vertices of the uploaded background
+        self.bg_ne = 0        # ... and its tets
         self.npts = 0
         self.n_new_tets = 0
 
@@ -134,6 +137,7 @@ class Transfer:
                                                  imet if arr else -1), "pmx_upload_background")
         self.sizes = [v.size for v in views[: len(arr)]]
         self.bg_np = m.np
+        self.bg_ne = m.ne
 
     def copy_required(self, perm: np.ndarray | None = None, copy_metric: bool = True):
         """pmx_copy_required: frozen (MG_REQ) background points' values into the
@@ -528,6 +532,29 @@ class Transfer:
                   "pmx_prilen_device")
         del keep
 
+    def metis_graph(self, met_rid_typ: int = 0, weights: bool = True):
+        """PMMG_graph_meshElts2metis of the uploaded (or promoted) group
+        (pmx_metis_graph): (xadj (ne+1,), adjncy (nadjncy,), adjwgt (nadjncy,)
+        or None) as int32, the idx_t of a default Metis build.  weights=False:
+        the reference's *adjwgt == NULL (distribution time, last iteration)."""
+        ne = self.bg_ne
+        xadj = np.empty(ne + 1, np.int32)
+        adjncy = np.empty(max(4 * ne, 1), np.int32)
+        adjwgt = np.empty(max(4 * ne, 1), np.int32) if weights else None
+        n = C.c_int64(0)
+        i32 = lambda a: a.ctypes.data_as(N.i32ptr) if a is not None else None
+        self._chk(self.lib.pmx_metis_graph(self.ctx, met_rid_typ, i32(xadj), i32(adjncy), i32(adjwgt),
+                                           len(adjncy), C.byref(n)), "pmx_metis_graph")
+        return xadj, adjncy[: n.value], (adjwgt[: n.value] if weights else None)
+
+    def face_weights(self, faces: np.ndarray, met_rid_typ: int = 0) -> np.ndarray:
+        """PMMG_computeWgt as doubles for the listed faces of the uploaded
+        group, faces[i] = 12*ie + 3*ifac (+ iloc): pmx_face_weights."""
+        f = np.ascontiguousarray(faces, np.int32)
+        w = np.zeros(len(f))
+        self._chk(self.lib.pmx_face_weights(self.ctx, met_rid_typ, len(f), _ip(f), _dp(w)), "pmx_face_weights")
+        return w
+
     def upload_new_tets(self, tets: np.ndarray):
         """The new mesh's tets, (ne+1, 4) with 0-based point indices (v[0] < 0:
         deleted), for pmx_promote_background / pmx_new_mesh_qual."""
@@ -554,6 +581,7 @@ class Transfer:
         self._chk(self.lib.pmx_promote_background(self.ctx, C.byref(mv), len(arr), views),
                   "pmx_promote_background")
         self.bg_np = self.npts              # the promoted points are the background's vertices
+        self.bg_ne = new_mesh.ne
         self.npts = 0
 
     def new_mesh_qual(self, tets: np.ndarray | None, opt: int = N.INQUA, dev_ptr: int = 0,
