@@ -18,6 +18,112 @@ def lin_field(x):
     return (1.0 + 2.0 * x[:, 0] - 3.0 * x[:, 1] + 0.5 * x[:, 2])[:, None]
 
 
+def generic_tensor(x):
+    """A smooth generic SPD tensor field on unit-box coordinates,
+    R(x) diag(1 / h_i(x)^2) R(x)^T: three different sizes, R the rotation by
+    an angle that varies with x about a skew axis.  No two diagonal entries
+    and no two off-diagonal entries are equal (test_reference_cpu checks them
+    pairwise different by more than 1e-3 relative at every vertex), so a read
+    of the wrong component changes the result.  Stored (m11, m12, m13, m22,
+    m23, m33), shape (n, 6)."""
+    x = np.asarray(x, np.float64)
+    k = np.array([0.3, -0.5, 0.81])
+    k = k / np.sqrt((k * k).sum())
+    ang = 2.86 + 0.325 * x[:, 0] - 0.225 * x[:, 1] + 0.1 * x[:, 2]
+    h = np.stack([0.02 + 0.05 * x[:, 0], 0.08 + 0.1 * x[:, 1] * x[:, 2], 0.2 - 0.1 * x[:, 2]], 1)
+    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+    R = (np.eye(3)[None] + np.sin(ang)[:, None, None] * K[None]
+         + (1.0 - np.cos(ang))[:, None, None] * (K @ K)[None])        # Rodrigues
+    S = np.einsum("nij,nj,nkj->nik", R, 1.0 / (h * h), R)
+    S = 0.5 * (S + S.transpose(0, 2, 1))
+    return np.ascontiguousarray(np.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], 1))
+
+
+def unit_box(f):
+    """f evaluated on coordinates normalised to the points' bounding box (for
+    meshes that are not the unit cube)."""
+    def g(x):
+        lo, hi = x.min(axis=0), x.max(axis=0)
+        return f((x - lo) / (hi - lo))
+    return g
+
+
+def graded_iso_scaled(m):
+    """mesh.graded_iso_metric for a mesh that is not a unit Kuhn cube: the same
+    grading on bounding-box coordinates, scaled to the mesh's mean edge length
+    (metric edge lengths spread over all the bins of PMMG_prilen), (np+1, 1)."""
+    t = m.tet[1:]
+    e = np.concatenate([m.xyz[t[:, j]] - m.xyz[t[:, i]] for i, j in ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))])
+    lbar = np.sqrt((e * e).sum(1)).mean()
+
+    def f(x):
+        return (0.8 * lbar * np.exp(1.6 * (x.sum(axis=1) - 1.5)))[:, None]
+    return M.on_vertices(m, unit_box(f))
+
+
+def ridge_tags(m, seed=3):
+    """Ridge points on the x < 0.4 slab (mixed with singular / non-manifold
+    ones that are NOT ridge points for the filter)."""
+    GEO, REQ, NOM, CRN = 2, 4, 8, 32
+    rng = np.random.default_rng(seed)
+    tags = np.zeros(m.np + 1, np.uint16)
+    slab = np.nonzero(m.xyz[:, 0] < 0.4)[0]
+    slab = slab[slab > 0]
+    tags[slab] = GEO
+    extra = rng.choice(slab, size=len(slab) // 6, replace=False)
+    tags[extra[: len(extra) // 3]] |= REQ
+    tags[extra[len(extra) // 3: 2 * len(extra) // 3]] |= NOM
+    tags[extra[2 * len(extra) // 3:]] |= CRN
+    return tags
+
+
+def generic_tensor_edges(m, met):
+    """A copy of the tensor field `met` with special rows planted at interior
+    vertices no two of which share a tet:
+
+    * "zero": exactly zero off-diagonals;
+    * "below" / "above": the largest off-diagonal magnitude 0.5e-6 / 2e-6, on
+      either side of MMG5_invmat's absolute threshold (1e-6) for inverting a
+      matrix as its diagonal;
+    * "singular": [1, 1, 0, 1, 0, 1], which does not invert.
+
+    Returns (met, {"zero": [...], "below": [...], "above": [...], "singular": [...]})."""
+    met = np.array(met, np.float64, copy=True)
+    onb = np.zeros(m.np + 1, bool)
+    if m.nt:
+        onb[m.tria[1:].ravel()] = True
+    taken = np.zeros(m.np + 1, bool)          # vertices of the tets of a planted vertex
+    inc = [[] for _ in range(m.np + 1)]
+    for k in range(1, m.ne + 1):
+        for v in m.tet[k]:
+            inc[v].append(k)
+    names = ("zero", "below", "above", "singular", "zero", "below", "above")
+    planted = {n: [] for n in names}
+    cand = np.random.default_rng(17).permutation(np.arange(1, m.np + 1))
+    it = iter(names)
+    name = next(it)
+    for ip in cand:
+        ball = np.unique(m.tet[inc[ip]].ravel()) if inc[ip] else np.zeros(0, np.int64)
+        if onb[ip] or not len(ball) or taken[ball].any():
+            continue
+        taken[ball] = True
+        d = met[ip, [0, 3, 5]].copy()
+        if name == "zero":
+            met[ip] = [d[0], 0.0, 0.0, d[1], 0.0, d[2]]
+        elif name == "below":
+            met[ip] = [d[0], 0.5e-6, -0.2e-6, d[1], 0.3e-6, d[2]]
+        elif name == "above":
+            met[ip] = [d[0], -0.7e-6, 2e-6, d[1], 1.1e-6, d[2]]
+        else:
+            met[ip] = [1.0, 1.0, 0.0, 1.0, 0.0, 1.0]
+        planted[name].append(int(ip))
+        name = next(it, None)
+        if name is None:
+            break
+    assert name is None, "not enough independent interior vertices"
+    return met, planted
+
+
 def cube_case(n: int, metric: str = "iso", surface: bool = True, fields: bool = True,
               seed_pts: int = 12345):
     m = M.kuhn_cube(n)
@@ -132,7 +238,7 @@ TAG_REF, TAG_GEO, TAG_REQ, TAG_NOM, TAG_BDY, TAG_CRN = 1, 2, 4, 8, 16, 32
 IARE = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
 
 
-def cube_surface(m, seed: int = 5, noise: float = 0.05, ridge_frac: float = 1.0):
+def cube_surface(m, seed: int = 5, noise: float = 0.05, ridge_frac: float = 1.0, base=None):
     """Mmg-like surface data of a Kuhn mesh of the unit cube, the way
     MMG3D_analys leaves it (synthetic: the kernels only read it):
 
@@ -147,7 +253,8 @@ def cube_surface(m, seed: int = 5, noise: float = 0.05, ridge_frac: float = 1.0)
       that the curved-length formulas see non-trivial normals;
     * the metric in Mmg's ridge storage at the non-singular ridge points
       ((tangent, in-surface 1 / 2, normal 1 / 2) sizes^-2), a shock tensor
-      elsewhere (ridge_frac < 1: only that fraction of the ridge points).
+      elsewhere (ridge_frac < 1: only that fraction of the ridge points;
+      base: the tensor field used off the ridge rows instead of the shock one).
 
     Returns (tags (np+1,), surface dict for Transfer.upload_surface /
     oracle.prilen, met (np+1, 6))."""
@@ -207,7 +314,7 @@ def cube_surface(m, seed: int = 5, noise: float = 0.05, ridge_frac: float = 1.0)
                     t6[ia] |= TAG_GEO
         xtag.append(t6)
         xt[k] = len(xtag) - 1
-    met = M.on_vertices(m, M.shock_metric)
+    met = M.on_vertices(m, M.shock_metric if base is None else base)
     rid = np.nonzero(((tag & TAG_GEO) != 0) & ((tag & (TAG_CRN | TAG_REQ | TAG_NOM)) == 0))[0]
     rid = rid[: int(len(rid) * ridge_frac)]
     h = rng.uniform(0.02, 0.2, size=(len(rid), 5))

@@ -15,7 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import bits_equal, compare_volume
+from helpers import bits_equal, compare_volume, generic_tensor
 from oracle import oracle as O
 from parmmg_amd import mesh as M
 
@@ -63,7 +63,7 @@ def write_case(d, metric="iso", n=6, n2=7):
     ntag[req] = otag[req]
     nxyz = new.xyz.copy()
     nxyz[req] = old.xyz[req]
-    f = M.shock_metric if metric == "ani" else M.iso_metric
+    f = {"ani": M.shock_metric, "gen": generic_tensor, "iso": M.iso_metric}[metric]
     omet = M.on_vertices(old, f)
     ofld = M.on_vertices(old, M.level_set)
     files = dict(old_xyz=old.xyz, old_tet=old.tet, old_tag=otag, old_met=omet, old_fld=ofld,
@@ -146,9 +146,13 @@ def test_adapter_ani_ridge_metric(tmp_path):
     MMG5_lenedg_ani) and PMMG_prilen(parmesh,0,1) (src/libparmmg.c:185) in
     classic storage (MMG5_lenedg33_ani): both equal the oracle's restatement
     bit for bit."""
+    ani_ridge_case(tmp_path, "ani")
+
+
+def ani_ridge_case(tmp_path, metric):
     from helpers import cube_surface
     d = str(tmp_path)
-    old, new, otag, ntag, nxyz, omet, ofld, req = write_case(d, "ani")
+    old, new, otag, ntag, nxyz, omet, ofld, req = write_case(d, metric)
     stag, surf, _ = cube_surface(new, noise=0.08)
     for k, a in dict(new_xt=surf["xt"].astype(np.int32), new_xtag=surf["xtag"].astype(np.uint16),
                      new_pn=surf["n"], new_xp=surf["xp"].astype(np.int32), new_n1=surf["n1"],
@@ -175,6 +179,35 @@ def test_adapter_ani_ridge_metric(tmp_path):
     o0 = O.tetra_qual(mesh_new, met)
     assert np.array_equal(q1[1:], o1[1:]) and np.array_equal(q0[1:], o0[1:])
     assert np.count_nonzero(q1[1:] != q0[1:]) > 0       # the ridge points change the mean
+    return old, new, ntag, nxyz, omet, ofld, req, met
+
+
+@pytest.mark.gpu
+def test_adapter_generic_tensor_metric(tmp_path):
+    """The same calls with a generic tensor metric (six different components
+    per vertex, helpers.generic_tensor): the binding's strided AoS packing
+    must carry every component to its place -- the interpolated metric equals
+    the plain device step's bit for bit, the frozen points keep the old rows,
+    and the statistics above equal the oracle's on it."""
+    old, new, ntag, nxyz, omet, ofld, req, met = ani_ridge_case(tmp_path, "gen")
+    assert np.array_equal(met[req], omet[req])
+    from parmmg_amd.transfer import Transfer
+    x, t = nxyz[1:], ntag[1:]
+    tr = Transfer(0)
+    try:
+        tr.upload_background(old, [omet, ofld], 0)
+        tr.upload_points(x, t, tets_mmg=new.tet)
+        tr.run()
+        g = tr.download()
+    finally:
+        tr.close()
+    live = (t & M.TAG_REQ) == 0
+    assert live.sum() > 0 and bits_equal(g.sols[0][live], met[1:][live]).all()
+    o = O.Oracle(old)
+    outs, elem, st, *_ = o.interp(x, t, [omet, ofld], imet=0)
+    fld = np.fromfile(os.path.join(str(tmp_path), "out_fld.bin")).reshape(new.np + 1, 1)
+    c = compare_volume(o, x, t, ([met[1:], fld[1:]], g.elem, g.status), (outs, elem, st), [omet, ofld])
+    assert c["same"] >= c["nvol"] - 3
 
 
 @pytest.mark.gpu

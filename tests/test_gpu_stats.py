@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import compare_volume, cube_case, split_partitions
+from helpers import compare_volume, cube_case, ridge_tags, split_partitions
 from oracle import oracle as O
 from parmmg_amd import _native as N
 from parmmg_amd import mesh as M
@@ -50,21 +50,6 @@ def assert_qual_equal(h, ho):
         assert h[f] == ho[f], f
     assert h["his"] == ho["his"]
     assert abs(h["avg"] - ho["avg"]) <= 1e-12 * abs(ho["avg"])
-
-
-def ridge_tags(m, seed=3):
-    """Ridge points on the x < 0.4 slab (mixed with singular / non-manifold
-    ones that are NOT ridge points for the filter)."""
-    rng = np.random.default_rng(seed)
-    tags = np.zeros(m.np + 1, np.uint16)
-    slab = np.nonzero(m.xyz[:, 0] < 0.4)[0]
-    slab = slab[slab > 0]
-    tags[slab] = GEO
-    extra = rng.choice(slab, size=len(slab) // 6, replace=False)
-    tags[extra[: len(extra) // 3]] |= REQ
-    tags[extra[len(extra) // 3: 2 * len(extra) // 3]] |= NOM
-    tags[extra[2 * len(extra) // 3:]] |= CRN
-    return tags
 
 
 @pytest.mark.parametrize("metric", ["iso", "ani"])

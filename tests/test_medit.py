@@ -148,3 +148,48 @@ def test_errors_are_reported(tmp_path):
     q.write_text("MeshVersionFormatted 2\nDimension 3\nVertices\n3\n0 0 0 0\n1 1\n")
     with pytest.raises(RuntimeError, match="truncated"):
         MD.read_mesh(str(q))
+
+
+def test_tensor_order_hand_written(tmp_path):
+    """A hand-written ASCII .sol with six distinct tensor values per vertex in
+    Medit's order (m11 m12 m22 m13 m23 m33): both readers return Mmg's order
+    (m11 m12 m13 m22 m23 m33), and the file the C writer makes of that holds
+    Medit's order again."""
+    p = str(tmp_path / "hand.sol")
+    with open(p, "w") as f:
+        f.write("MeshVersionFormatted 2\n\nDimension 3\n\nSolAtVertices\n3\n2 1 3\n"
+                "0.5 11 12 22 13 23 33\n"
+                "1.5 111 112 122 113 123 133\n"
+                "2.5 211 212 222 213 223 233\n\nEnd\n")
+    want = np.array([[0, 0, 0, 0, 0, 0], [11, 12, 13, 22, 23, 33], [111, 112, 113, 122, 123, 133],
+                     [211, 212, 213, 222, 223, 233]], np.float64)
+    for read in (MD.read_sol, M.read_medit_sol):
+        got = read(p)
+        assert len(got) == 2 and got[1].shape == (4, 6)
+        assert np.array_equal(got[0][1:, 0], [0.5, 1.5, 2.5])
+        assert np.array_equal(got[1][1:], want[1:]), read
+    q = str(tmp_path / "back.sol")
+    MD.write_sol(q, [want])
+    tok = _tokens(q)
+    i = tok.index("SolAtVertices")
+    assert tok[i + 1: i + 4] == ["3", "1", "3"]
+    vals = np.array(tok[i + 4: i + 4 + 18], np.float64).reshape(3, 6)
+    assert np.array_equal(vals[0], [11, 12, 22, 13, 23, 33]) and np.array_equal(vals[2], [211, 212, 222, 213, 223, 233])
+
+
+@pytest.mark.parametrize("ext", ["sol", "solb"])
+def test_generic_tensor_round_trip(tmp_path, ext):
+    """A tensor field whose six components all differ (helpers.generic_tensor),
+    ASCII and binary: bit for bit, column by column."""
+    from helpers import generic_tensor
+    m = M.kuhn_cube(4, seed=3)
+    met = M.on_vertices(m, generic_tensor)
+    cols = met[1:]
+    assert all(np.all(cols[:, i] != cols[:, j]) for i in range(6) for j in range(i + 1, 6))
+    p = str(tmp_path / f"g.{ext}")
+    MD.write_sol(p, [met])
+    got, = MD.read_sol(p)
+    assert np.array_equal(got[1:].view(np.int64), met[1:].view(np.int64))
+    if ext == "sol":
+        a, = M.read_medit_sol(p)
+        assert np.array_equal(a[1:], met[1:])
