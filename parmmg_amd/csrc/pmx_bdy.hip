@@ -1029,16 +1029,13 @@ static bool node_trias_counting(pmx_ctx *c, hipStream_t s) {
   return true;
 }
 
-bool pmx_ctx::build_node_trias(hipStream_t s, int force, bool check) {
+bool pmx_ctx::build_node_trias(hipStream_t s, bool check) {
   const int64_t m = 3 * nt;
   if (m < 1) return true;
-  if (fan_rot && force == 0 && check) {
-    // the upload's check again (a FRESH step: what a new background costs):
-    // the vertices' fan owners beside the rotation
-    return fan_rotation(s, d_wfar.p + 2, true);
-  }
-  if (fan_rot && force == 0) return fan_rotation(s, d_wfar.p + 2, false);
-  if (np <= 5 * m || force == 1) {
+  // check: the upload's check again (a FRESH step: what a new background
+  // costs), the vertices' fan owners beside the rotation
+  if (fan_rot) return fan_rotation(s, d_wfar.p + 2, check);
+  if (np <= 5 * m) {
     if (!node_trias_counting(this, s)) return false;
     if (hipGetLastError() != hipSuccess) {
       err = "node trias: launch";
@@ -1125,13 +1122,11 @@ static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap = false) {
 // ovf_threads: the overflow pass's threads, OVF_THREADS unless the caller
 // sized the workspace for more (the sequential mode's speculative pass, whose
 // walks from the predecessors' trias overflow by the thousand)
-static void launch_bdy_walks(const BdyArgs &B, int *ows, int exp, hipStream_t s, int ovf_threads = OVF_THREADS,
+static void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_threads = OVF_THREADS,
                              bool hashed = false, bool pointmap = false) {
   const int64_t nb = (B.nlist + 255) / 256;
   if (pointmap)
     hipLaunchKernelGGL((k_locate_bdy<BDY_CAP, true>), dim3((unsigned)nb), dim3(256), 0, s, B);
-  else if (exp == 10)                    // A/B: the r01-r03 8-entry private lists
-    hipLaunchKernelGGL(k_locate_bdy<BDY_CAP / 2>, dim3((unsigned)nb), dim3(256), 0, s, B);
   else
     hipLaunchKernelGGL(k_locate_bdy<BDY_CAP>, dim3((unsigned)nb), dim3(256), 0, s, B);
   if (hashed)
@@ -1169,7 +1164,7 @@ bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
     hipLaunchKernelGGL(k_tria_hint_build, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(256), 0, s,
                        d_tris.p, d_xyz.p, nt, d_tgrid, tgd);
   }
-  launch_bdy_walks(bdy_args(this, a, pointmap), d_ows.p, a.exp, s, OVF_THREADS, false, pointmap);
+  launch_bdy_walks(bdy_args(this, a, pointmap), d_ows.p, s, OVF_THREADS, false, pointmap);
   return hipGetLastError() == hipSuccess;
 }
 
@@ -1446,7 +1441,7 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
     if (!pmx_dgrow(this, d_ows, ws_ints) ||
         !ck(hipMemsetAsync(d_ows.p, 0, ws_ints * sizeof(int), s), "memset"))
       return false;
-    launch_bdy_walks(B, d_ows.p, a.exp, s, seq_ovf, true);
+    launch_bdy_walks(B, d_ows.p, s, seq_ovf, true);
     // 3. the replay, on the reference's state
     if (!ck(hipMemsetAsync(d_sqtf.p, 0, (size_t)(nt + 1) * sizeof(int), s), "memset") ||
         !ck(hipMemsetAsync(d_sqpf.p, 0x80, (size_t)(np + 1) * sizeof(int), s), "memset"))

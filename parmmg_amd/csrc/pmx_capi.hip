@@ -101,23 +101,12 @@ static unsigned host_threads() {
 }
 // streaming (non-temporal) 16-B stores into the pinned staging: the host
 // never reads those lines again, and a plain store first reads each line for
-// ownership (a third of the packing traffic).  PMX_NT_STORES=0: plain stores,
-// for the A/B.  A pass ends with a full fence before its DMA is issued.
+// ownership (a third of the packing traffic).  A pass ends with a full fence
+// before its DMA is issued.
 typedef int pmx_v4i __attribute__((ext_vector_type(4)));
-static bool nt_stores() {
-  static const bool on = [] {
-    const char *e = getenv("PMX_NT_STORES");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-static inline void st4(int4 *p, int a, int b, int c, int d, bool nt) {
-  if (nt) {
-    const pmx_v4i v = {a, b, c, d};
-    __builtin_nontemporal_store(v, (pmx_v4i *)p);
-  } else {
-    *p = make_int4(a, b, c, d);
-  }
+static inline void st4(int4 *p, int a, int b, int c, int d) {
+  const pmx_v4i v = {a, b, c, d};
+  __builtin_nontemporal_store(v, (pmx_v4i *)p);
 }
 static int64_t host_threads_min() {
   static const int64_t M = [] {
@@ -250,7 +239,7 @@ bool pmx_download_qual(pmx_ctx *ctx, const double *dev, int64_t ne, double *qual
   if (!st) return false;
   const double *h = (const double *)st;
   char *out = (char *)qual;
-  const bool nt_q = !dense && nt_stores() && ((uintptr_t)out % 8) == 0 && stride % 8 == 0;
+  const bool nt_q = !dense && ((uintptr_t)out % 8) == 0 && stride % 8 == 0;
   const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(8, (ne + 1) >> 20));
   for (int64_t c = 0; c < nch; c++) {
     const int64_t lo = (ne + 1) * c / nch, hi = (ne + 1) * (c + 1) / nch;
@@ -403,18 +392,6 @@ pmx_ctx *pmx_create(int device) {
   if (hipSetDevice(device) != hipSuccess) return nullptr;
   pmx_ctx *ctx = new pmx_ctx();
   ctx->device = device;
-  // PMX_SIDE_CUS=N (measurement): the side stream on CUs [0, N), the main
-  // stream on the rest (hipExtStreamCreateWithCUMask)
-  int side_cus = 0;
-  if (const char *e = getenv("PMX_SIDE_CUS")) side_cus = atoi(e);
-  int ncu = 0;
-  hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-  std::vector<uint32_t> mside, mmain;
-  if (side_cus > 0 && side_cus < ncu) {
-    mside.assign((size_t)(ncu + 31) / 32, 0u);
-    mmain.assign((size_t)(ncu + 31) / 32, 0u);
-    for (int c = 0; c < ncu; c++) (c < side_cus ? mside : mmain)[c / 32] |= 1u << (c % 32);
-  }
   // HIP maps a process's streams onto a few hardware queues (4 by default,
   // GPU_MAX_HW_QUEUES) in creation order: a second context's streams share
   // the first one's queues, and two streams on one queue run one after the
@@ -424,35 +401,12 @@ pmx_ctx *pmx_create(int device) {
   // (PMX_interpMetricsAndFields runs two groups' steps side by side).
   static std::atomic<unsigned> n_created{0};
   const bool odd = (n_created.fetch_add(1) & 1u) != 0;
-  // PMX_STREAM_PRIO=1 (A/B): the main stream at the device's greatest
-  // priority, the orphan-mark stream at its least, so that the walk's
-  // critical prefix (derived data, hint build) is dispatched first
-  static const bool prio = [] {
-    const char *e = getenv("PMX_STREAM_PRIO");
-    return e && e[0] == '1';
-  }();
-  int p_least = 0, p_greatest = 0;
-  if (prio) hipDeviceGetStreamPriorityRange(&p_least, &p_greatest);
-  auto mk_main = [&] {
-    if (mmain.empty() && prio) return hipStreamCreateWithPriority(&ctx->own, hipStreamNonBlocking, p_greatest);
-    return mmain.empty() ? hipStreamCreateWithFlags(&ctx->own, hipStreamNonBlocking)
-                         : hipExtStreamCreateWithCUMask(&ctx->own, (uint32_t)mmain.size(), mmain.data());
-  };
-  auto mk_up = [&] {
-    return prio ? hipStreamCreateWithPriority(&ctx->up, hipStreamNonBlocking, p_least)
-                : hipStreamCreateWithFlags(&ctx->up, hipStreamNonBlocking);
-  };
-  auto mk_side = [&] {
-    return mside.empty() ? hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking)
-                         : hipExtStreamCreateWithCUMask(&ctx->side, (uint32_t)mside.size(), mside.data());
-  };
+  auto mk = [](hipStream_t *st) { return hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess; };
   bool sok;
   if (!odd)
-    sok = mk_main() == hipSuccess && mk_side() == hipSuccess && mk_up() == hipSuccess &&
-          hipStreamCreateWithFlags(&ctx->topo, hipStreamNonBlocking) == hipSuccess;
+    sok = mk(&ctx->own) && mk(&ctx->side) && mk(&ctx->up) && mk(&ctx->topo);
   else
-    sok = hipStreamCreateWithFlags(&ctx->topo, hipStreamNonBlocking) == hipSuccess && mk_up() == hipSuccess &&
-          mk_main() == hipSuccess && mk_side() == hipSuccess;
+    sok = mk(&ctx->topo) && mk(&ctx->up) && mk(&ctx->own) && mk(&ctx->side);
   ctx->stream = ctx->own;
   if (!sok ||
       hipEventCreateWithFlags(&ctx->ev_topo, hipEventDisableTiming) != hipSuccess ||
@@ -678,7 +632,6 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
   const char *tc = (const char *)m->tetra_v;
   const int *adja_in = m->adja;
   bool bad = false;
-  const bool ntst = nt_stores();
   const int64_t ntc = std::max<int64_t>(1, std::min<int64_t>(8, ne >> 20));
   for (int64_t c = 0; c < ntc; c++) {
     const int64_t klo = (c == 0) ? 0 : 1 + ne * c / ntc, khi = 1 + ne * (c + 1) / ntc;
@@ -690,11 +643,11 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
         // MG_EOK) must name vertices 1..np and neighbours 0..ne
         const bool valid = v[0] > 0;
         if (dev_adja) {
-          if (!valid) { st4(&htv[k], 0, 0, 0, 0, ntst); }
+          if (!valid) { st4(&htv[k], 0, 0, 0, 0); }
           else {
             for (int l = 0; l < 4; l++)
               if (v[l] < 1 || v[l] > np) b = true;
-            st4(&htv[k], v[0], v[1], v[2], v[3], ntst);
+            st4(&htv[k], v[0], v[1], v[2], v[3]);
           }
         } else {
           TetRec &r = ht[(size_t)k];
@@ -1000,7 +953,6 @@ bool pmx_ctx::pack_new_tets() {
   const char *tc = (const char *)pv->tetra_v;
   bool bad = false;
   htv[0] = make_int4(0, 0, 0, 0);
-  const bool nt = nt_stores();
   const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(8, ntet >> 20));
   for (int64_t c = 0; c < nch; c++) {
     const int64_t lo = (c == 0) ? 0 : 1 + ntet * c / nch, hi = 1 + ntet * (c + 1) / nch;
@@ -1008,14 +960,14 @@ bool pmx_ctx::pack_new_tets() {
       bool b = false;
       for (int64_t k = k0; k < k1; k++) {
         const int *v = (const int *)(tc + k * pv->tetra_stride);
-        if (v[0] <= 0) { st4(&htv[k], 0, 0, 0, 0, nt); continue; }   // !MG_EOK
+        if (v[0] <= 0) { st4(&htv[k], 0, 0, 0, 0); continue; }   // !MG_EOK
         int w[4];
         for (int l = 0; l < 4; l++) {
           int64_t jj = (int64_t)v[l] - pv->first;
           if (jj < 0 || jj >= n) { b = true; jj = 0; }
           w[l] = (int)(jj + 1);
         }
-        st4(&htv[k], w[0], w[1], w[2], w[3], nt);
+        st4(&htv[k], w[0], w[1], w[2], w[3]);
       }
       if (b) __atomic_store_n(&bad, true, __ATOMIC_RELAXED);
       std::atomic_thread_fence(std::memory_order_seq_cst);
@@ -1171,11 +1123,9 @@ static void fill_vol_args(pmx_ctx *ctx, const SolDesc &sd, const pmx_run_opts &o
 }
 
 // pmx_run_opts.flags: the public PMX_RUN_* bits, plus the experiment switch
-// in bits 16-23 (VolArgs.exp).  Switches that keep the results bit for bit
-// (A/Bs of layouts, launch shapes and stream order) are always accepted; the
-// measurement switches that skip work (4: no interpolation, 5: hint only)
-// only when PMX_EXPERIMENTS=1 is set in the environment; anything else is
-// refused, so that a stray bit never changes results silently.
+// in bits 16-23 (VolArgs.exp): 6, 17 and 18, which keep the results bit for
+// bit.  Anything else is refused, so that a stray bit never changes results
+// silently.
 static bool run_flags_valid(int flags, std::string *err) {
   const int pub = PMX_RUN_REFERENCE_WALK | PMX_RUN_NO_INLINE_TIES | PMX_RUN_RECORD_STARTS |
                   PMX_RUN_SERIAL_SURFACE | PMX_RUN_FRESH_BACKGROUND | PMX_RUN_DEBUG_BARRIER_TIMEOUT |
@@ -1186,19 +1136,11 @@ static bool run_flags_valid(int flags, std::string *err) {
     return false;
   }
   const int e = (flags >> PMX_RUN_EXP_SHIFT) & 0xff;
-  switch (e) {
-    case 0: case 6: case 9: case 10: case 11: case 12: case 13: case 15: case 16: case 17: case 18: case 19: case 20: case 21: case 22: case 23: case 24: case 25: case 26:
-      return true;
-    case 4: case 5: case 14: {
-      const char *v = getenv("PMX_EXPERIMENTS");
-      if (v && v[0] == '1') return true;
-      *err = "pmx_run: measurement switch needs PMX_EXPERIMENTS=1";
-      return false;
-    }
-    default:
-      *err = "pmx_run: unknown experiment switch";
-      return false;
+  if (e != 0 && e != 6 && e != 17 && e != 18) {
+    *err = "pmx_run: unknown experiment switch";
+    return false;
   }
+  return true;
 }
 
 int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
@@ -1273,41 +1215,21 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
   // (on the side stream only once it has been forked from the main one: an
   // unforked side stream's event could precede ev[0])
   if (ev) CK(hipEventRecord(ev[3], bdy ? ss : st));
-  // exp 19 (A/B): the fans on the main stream ahead of the derived data (a
-  // few short kernels there, instead of passes starved on the side stream);
-  // exp 20: the same with the counting sort over the vertex ids
-  const int exp0 = (opts.flags >> PMX_RUN_EXP_SHIFT) & 0xff;
-  // exp 25 (A/B, r06): the fans (and a FRESH step's fan check) on the side
-  // stream after the classification, beside the walk instead of the prefix
-  const bool fans_late = exp0 == 25 && bdy && !serial;
-  if (bdy && csr && !fans_late) {
-    if (!ctx->build_node_trias(exp0 == 19 || exp0 == 20 ? st : ss, exp0 == 20 ? 1 : 0, fresh)) return 0;
+  if (bdy && csr) {
+    if (!ctx->build_node_trias(ss, fresh)) return 0;
     ctx->have_csr = true;
   }
   // the orphan marks on `up`, beside the derived data and the hint build
   // (the classification waits for them)
-  // exp 26 (A/B): the marks start after the derived data (which they slow
-  // by sharing the memory system), beside the latency-bound hint build only
-  const bool marks_after_derive = marks && exp0 == 26;
-  auto launch_marks = [&]() -> bool {
+  if (marks) {
     CK(hipEventRecord(ctx->ev_fork, st));
     CK(hipStreamWaitEvent(ctx->up, ctx->ev_fork, 0));
-    if (!ctx->mark_new_tets(ctx->up)) return false;
+    if (!ctx->mark_new_tets(ctx->up)) return 0;
     CK(hipEventRecord(ctx->ev_tets, ctx->up));
     ctx->tets_inflight = true;
-    return true;
-  };
-  if (marks && !marks_after_derive && !launch_marks()) return 0;
-  // exp 15 (A/B): no fixed-point copy of the vertices -- the hint build
-  // quantises the sampled tets' vertices itself -- and the tria normals on
-  // the surface stream
-  const int exp = (opts.flags >> PMX_RUN_EXP_SHIFT) & 0xff;
-  const bool hint_xyz = exp == 15 && (opts.hint_stride == 0 || opts.hint_stride == PMX_HINT_STRIDE);
+  }
   if (derive) {
-    if (hint_xyz)
-      launch_bg_derive(ctx->d_xyz.p, 0, ctx->grid, ctx->d_xyzq.p, ctx->d_tris.p, ctx->nt, ctx->d_trn.p,
-                       (bdy && !serial) ? side : st);
-    else if (bdy && !serial) {
+    if (bdy && !serial) {
       // the tria normals only feed the surface path: on its stream (r05:
       // the main stream's derived-data pass is the vertices alone)
       launch_bg_derive(ctx->d_xyz.p, ctx->np, ctx->grid, ctx->d_xyzq.p, ctx->d_tris.p, 0, ctx->d_trn.p, st);
@@ -1316,10 +1238,9 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
       launch_bg_derive(ctx->d_xyz.p, ctx->np, ctx->grid, ctx->d_xyzq.p, ctx->d_tris.p, ctx->nt,
                        ctx->d_trn.p, st);
     }
-    ctx->have_derived = !hint_xyz;
+    ctx->have_derived = true;
   }
   if (fresh && !ctx->rederive(st)) return 0;
-  if (marks_after_derive && !launch_marks()) return 0;
   if (ev) CK(hipEventRecord(ev[7], st));
   // the first-incident-element maps: derived background data like the tria
   // normals, after the records a FRESH step rebuilt, only for a flagged step
@@ -1341,18 +1262,13 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     if (pm) return;                          // no grid: the starts come with the classification
     launch_hint_build(packed ? ctx->d_tets_s.p : nullptr,
                       packed && ctx->samples_sorted ? ctx->d_tets_sk.p : nullptr, ctx->d_tets.p, ctx->ne,
-                      stride, ctx->d_grid.p, g_hint, hint_xyz ? nullptr : ctx->d_xyzq.p, ctx->d_xyz.p, st,
-                      exp == 16, exp == 21 ? 1024 : exp == 22 ? 64 : 256,
+                      stride, ctx->d_grid.p, g_hint, ctx->d_xyzq.p, st,
                       packed && ctx->samples_owner ? ctx->nsamp : -1);
   };
-  // exp 23 (A/B): the marks beside the walk instead -- the points
-  // classified without them, the orphans located and their rows reset at the
-  // end of the step (k_orphans), the r05 order of the hint build
-  const bool marks_late = marks && exp == 23;
-  const bool hint_first = marks && !marks_late && any_interp;
+  const bool hint_first = marks && any_interp;
   if (hint_first) hint_build();
-  if (marks && !marks_late) CK(hipStreamWaitEvent(st, ctx->ev_tets, 0));
-  if (!ctx->classify(st, marks && !marks_late, pm)) return 0;
+  if (marks) CK(hipStreamWaitEvent(st, ctx->ev_tets, 0));
+  if (!ctx->classify(st, marks, pm)) return 0;
   if (sd.metric_const)
     launch_const_metric(ctx->d_kind.p, n, ctx->d_out.p, S, sd.off[sd.imet], sd.size[sd.imet],
                         opts.hsiz, ctx->d_wmask.p, sd.imet, st);
@@ -1367,31 +1283,16 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     // the surface path on the side stream as soon as the points are
     // classified, latency-bound beside the hint build and the volume walk
     // (r03 A/B, profiles/r03_c{2,3,4}_sweep_surface_fork.log: C2 step 0.346 ->
-    // 0.338 ms, C3 / C4 within 0.1 %); exp 9: forked after the hint build
-    // (r01-r03 order: the r01 sweep had the hint build 40 % slower beside it)
-    auto fork_surface = [&]() -> bool {
-      if (!bdy || serial) return true;
+    // 0.338 ms, C3 / C4 within 0.1 %)
+    if (bdy && !serial) {
       CK(hipEventRecord(ctx->ev_fork2, st));
       CK(hipStreamWaitEvent(side, ctx->ev_fork2, 0));
-      if (fans_late && csr) {
-        if (!ctx->build_node_trias(side, 0, fresh)) return false;
-        ctx->have_csr = true;
-      }
-      if (!ctx->launch_bdy(A, side, pm)) return false;
+      if (!ctx->launch_bdy(A, side, pm)) return 0;
       if (ev) CK(hipEventRecord(ev[5], side));
       CK(hipEventRecord(ctx->ev_join, side));
-      return true;
-    };
-    const bool early = A.exp != 9;
-    if (early && !fork_surface()) return 0;
-    if (!hint_first) hint_build();
-    if (exp == 13 && A.wrec && !pm) {
-      if (!dgrow(ctx, ctx->d_hrec, (size_t)(2 * ctx->gcells))) return 0;
-      launch_hint_inline(ctx->d_grid.p, ctx->gcells, ctx->d_wrec.p, ctx->d_hrec.p, st);
-      A.hrec = ctx->d_hrec.p;
     }
+    if (!hint_first) hint_build();
     if (ev) CK(hipEventRecord(ev[1], st));
-    if (!early && !fork_surface()) return 0;
     if (ctx->nq_vol_ub) launch_walk(A, st, pm);
     if (ev) CK(hipEventRecord(ev[2], st));
     if (bdy && !serial) {
@@ -1423,12 +1324,6 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     if (opts.flags & (PMX_RUN_SEQUENTIAL_SURFACE | PMX_RUN_SEQUENTIAL_VOLUME)) {
       if (!ctx->seq_replay(A, st, sq_s, sq_v)) return 0;
       ctx->seq_stats_n = 1;
-    }
-    if (marks_late) {
-      CK(hipStreamWaitEvent(st, ctx->ev_tets, 0));
-      OrphanRows rr{ctx->d_wmask.p, ctx->d_elem.p, ctx->d_status.p, ctx->d_steps.p, ctx->d_start.p,
-                    ctx->d_edge.p, ctx->d_vertex.p, ctx->d_kind.p};
-      launch_orphans(ctx->d_qmark.p, n, (uint8_t)(sd.metric_const ? (1u << sd.imet) : 0u), rr, st);
     }
     if (ev) CK(hipEventRecord(ev[4], st));
   } else if (ev) {
@@ -1505,8 +1400,7 @@ static void scatter_rows(const pmx_ctx *ctx, const pmx_sol_view *new_sols, const
                          int64_t i0, int64_t i1) {
   const int S = ctx->sd.S;
   // streaming 8-B stores (no read for ownership of the caller's lines; the
-  // arrays are far larger than the caches anyway); PMX_NT_STORES=0: plain
-  const bool nt = nt_stores();
+  // arrays are far larger than the caches anyway)
   for (int64_t b0 = i0; b0 < i1; b0 += 1024) {
     const int64_t b1 = std::min(i1, b0 + 1024);
     for (int s = 0; s < ctx->sd.nsol; s++) {
@@ -1518,19 +1412,15 @@ static void scatter_rows(const pmx_ctx *ctx, const pmx_sol_view *new_sols, const
         if (!(wm[i] & bit)) continue;
         const double *src = h + i * S + off;
         double *d = dst + i * sz;
-        if (nt) {
-          for (int j = 0; j < sz; j++) {
-            long long bits;
-            memcpy(&bits, &src[j], sizeof bits);
-            __builtin_nontemporal_store(bits, (long long *)&d[j]);
-          }
-        } else {
-          for (int j = 0; j < sz; j++) d[j] = src[j];
+        for (int j = 0; j < sz; j++) {
+          long long bits;
+          memcpy(&bits, &src[j], sizeof bits);
+          __builtin_nontemporal_store(bits, (long long *)&d[j]);
         }
       }
     }
   }
-  if (nt) std::atomic_thread_fence(std::memory_order_seq_cst);   // the caller reads them next
+  std::atomic_thread_fence(std::memory_order_seq_cst);   // the caller reads them next
 }
 
 // pmx_download after a PMX_RUN_EAGER_DOWNLOAD step: the fields are (being)
@@ -1934,21 +1824,20 @@ int pmx_upload_new_tets(pmx_ctx *ctx, const int *tetra_v, int64_t tetra_stride, 
   h[0] = make_int4(0, 0, 0, 0);
   const char *tc = (const char *)tetra_v;
   bool bad = false;
-  const bool nt = nt_stores();
   // vertices renumbered from the points view (first..last) to 1..n: the
   // numbering of a promoted background
   par_for(1, ne + 1, [&](int64_t k0, int64_t k1) {
     bool b = false;
     for (int64_t k = k0; k < k1; k++) {
       const int *v = (const int *)(tc + k * tetra_stride);
-      if (v[0] <= 0) { st4(&h[k], 0, 0, 0, 0, nt); continue; }   // !MG_EOK
+      if (v[0] <= 0) { st4(&h[k], 0, 0, 0, 0); continue; }   // !MG_EOK
       int w[4];
       for (int l = 0; l < 4; l++) {
         const int64_t j = (int64_t)v[l] - first;
         if (j < 0 || j >= n) b = true;
         w[l] = (int)(j + 1);
       }
-      st4(&h[k], w[0], w[1], w[2], w[3], nt);
+      st4(&h[k], w[0], w[1], w[2], w[3]);
     }
     if (b) __atomic_store_n(&bad, true, __ATOMIC_RELAXED);
     std::atomic_thread_fence(std::memory_order_seq_cst);
@@ -2182,7 +2071,7 @@ void pmx_ctx::free_all() {
   dfree(d_kind); dfree(d_qmark); dfree(d_ctile); dfree(d_nsel); dfree(d_wmask); dfree(d_out); dfree(d_elem); dfree(d_status);
   dfree(d_steps); dfree(d_start); dfree(d_edge); dfree(d_vertex); dfree(d_list); dfree(d_found);
   dfree(d_bestk); dfree(d_best); dfree(d_ties); dfree(d_counts); dfree(d_vollist); dfree(d_bdylist);
-  dfree(d_vstat); dfree(d_bstat); dfree(d_hrec);
+  dfree(d_vstat); dfree(d_bstat);
   dfree(d_bphi); dfree(d_msol); dfree(d_mout); dfree(d_mwm);
   dfree(d_qsrc); dfree(d_pstart); dfree(d_pmap); dfree(d_pmcnt);
   have_src = have_pmap = false;
@@ -2204,7 +2093,6 @@ void pmx_ctx::free_all() {
   have_bg = have_pts = ran = have_derived = have_tetv = have_qual = have_ptag = have_qtag = have_csr = false;
   have_surf = false;
   dfree(d_etag); dfree(d_pn); dfree(d_xpn); dfree(d_pxp); dfree(d_pedge_tag);
-  dfree(d_pbcnt); dfree(d_pboff); dfree(d_pbrec); dfree(d_pbtmp);
   dfree(d_gdeg); dfree(d_gxadj); dfree(d_gadj); dfree(d_gwgt); dfree(d_gface); dfree(d_gflag); dfree(d_gtmp); dfree(d_gfw);
   graph_ev_n = 0;
   have_ntet = false;

@@ -16,7 +16,7 @@ template <class T> struct DevBuf {
 // hint grid from every 4th tet: 1/4 of the stores and of the tet bytes of a
 // full build, at ~0.5 extra walk step (r01 measurements)
 #define PMX_HINT_STRIDE 4
-// pmx_run_opts.flags bits 16-23: the walk's measurement switch (VolArgs.exp; tools/walk_pmc.sh)
+// pmx_run_opts.flags bits 16-23: the run-flag experiment (VolArgs.exp): 6, 17, 18
 #define PMX_RUN_EXP_SHIFT 16
 // the walk takes the 32-B tet records instead of the compact ones when more
 // than 1/PMX_WREC_FAR_DIV of the tets have a far neighbour field (pmx_wrec.h)
@@ -25,8 +25,8 @@ template <class T> struct DevBuf {
 struct pmx_ctx {
   int device = 0;
   hipStream_t own = nullptr, stream = nullptr;
-  // the surface path runs on `side`, forked after the volume hint build and
-  // joined before the fallback: it overlaps the volume walk
+  // the surface path runs on `side`, forked once the points are classified
+  // and joined before the fallback: it overlaps the hint build and the volume walk
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr;
   hipEvent_t ev_dl[8] = {};             // chunked download: one per chunk
@@ -137,7 +137,6 @@ struct pmx_ctx {
   DevBuf<int> d_qsrc, d_pstart;
   DevBuf<int2> d_ctile;                 // classification tile counts
   DevBuf<uint4> d_vstat, d_bstat;       // per-wave walk statistics
-  DevBuf<uint4> d_hrec;                 // exp 13: hint cells with their start record inline
   DevBuf<int> d_blist, d_olist, d_ows;
   // PMX_RUN_SEQUENTIAL_SURFACE (pmx_bdy.hip seq_surface): visit keys / order,
   // located / surface flags and their scan, bases | sequence | speculative
@@ -175,11 +174,6 @@ struct pmx_ctx {
   DevBuf<double> d_pn, d_xpn;
   DevBuf<int> d_pxp;
   DevBuf<uint16_t> d_pedge_tag;         // prilen: tags of the owned parallel edges
-  // prilen, edge-bucket variant (PMX_PRILEN_BUCKETS=1, A/B of the shell
-  // rotation): per-vertex counts / offsets / cursors and the candidate records
-  DevBuf<unsigned> d_pbcnt, d_pboff;
-  DevBuf<int4> d_pbrec;
-  DevBuf<char> d_pbtmp;
   // Metis element graph (pmx_metis_graph / pmx_face_weights): degrees (slot 0
   // = 0, so that their inclusive sum is xadj), xadj, adjncy, adjwgt, the
   // deleted-tet flag, cub scratch; the face list and its weights; the events
@@ -272,7 +266,7 @@ struct pmx_ctx {
   bool check_fans(hipStream_t s);
   // from d_tris, np, nt (pmx_bdy.hip); check: the rotation also re-counts every
   // vertex's trias, the upload's fan check (a FRESH step redoes it)
-  bool build_node_trias(hipStream_t s, int force = 0, bool check = false);
+  bool build_node_trias(hipStream_t s, bool check = false);
   // the new points: kinds, lists (pmx_capi.hip); marks: the orphan marks
   // (d_qmark) classify points in no valid new tet as KIND_ORPH
   // pointmap: also the start element of every compacted point from its

@@ -38,7 +38,6 @@ struct VolArgs {
                                 // [0, nq) per volume list entry, [nq, 2 nq) per surface list
                                 // entry, read by the PM instantiations of the walks (the
                                 // argument block, and with it every default kernel, unchanged)
-  const uint4 *hrec;            // exp 13: the hint cells with their start record inline
   GridDesc g;
   double *out;
   uint8_t *wmask;
@@ -59,11 +58,10 @@ struct VolArgs {
   int ref_walk;                 // 1: k_walk (reference-order walk) instead of k_walks
   int rec_start;                // write the start tet of every point (diagnostics)
   int far;                      // the compact records have far neighbour fields (pmx_wrec.h)
-  int exp;                      // measurement switch (tools/walk_pmc.sh): 0 production,
-                                // 4 no interpolation, 5 hint + hint record only,
+  int exp;                      // run-flag experiment (pmx_internal.h): 0 production,
+                                // 6 walk on the 32-B records,
                                 // 17 a record with a far neighbour field read whole,
-                                // 18 compact records whatever their far fields,
-                                // (pmx_run) 19 / 20 fans on the main stream
+                                // 18 compact records whatever their far fields
 };
 
 struct ExhArgs {
@@ -83,9 +81,7 @@ struct ExhArgs {
 // connectivity of tets 1, 1+stride, ... (stride == PMX_HINT_STRIDE), else the
 // tet records are read strided
 void launch_hint_build(const int4 *packed, const int *kidx, const TetRec *tets, int64_t ne, int stride, int *grid,
-                       GridDesc g, const unsigned long long *xyzq, const double *xyz, hipStream_t s,
-                       bool v0 = false, int bs = 256, int64_t nsamp = -1);
-void launch_hint_inline(const int *grid, int64_t cells, const WRec *wr, uint4 *hrec, hipStream_t s);
+                       GridDesc g, const unsigned long long *xyzq, hipStream_t s, int64_t nsamp = -1);
 // per-background derived data: fixed-point grid coordinates of the vertices
 // (hint centroids) and the unit normals of the boundary trias
 // (PMMG_precompute_triaNormals, src/locate_pmmg.c:68-90), one launch
@@ -218,8 +214,4 @@ struct StatArgs {
   const unsigned long long *par_key;
   int64_t npar;
   const uint8_t *par_pt;
-  // k_prilen's tet schedule: 0 = one contiguous range per workgroup; C > 0 =
-  // a moving front (each XCD's range dealt out in chunks of C batches,
-  // round-robin over that XCD's workgroups, all co-resident)
-  int sched_chunk;
 };

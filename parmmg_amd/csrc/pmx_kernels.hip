@@ -95,15 +95,10 @@ __global__ __launch_bounds__(256) void k_bg_derive(const double *__restrict__ xy
     trn[k] = Pt4{n.x * dd, n.y * dd, n.z * dd, a};
   }
 }
-// PMX_DERIVE_BLOCKS (A/B): the vertex pass's block cap
-static int64_t derive_blocks() {
-  const char *e = getenv("PMX_DERIVE_BLOCKS");
-  return e ? std::max<int64_t>(1, atoll(e)) : 8192;
-}
 void launch_bg_derive(const double *xyz, int64_t np, GridDesc g, unsigned long long *xyzq,
                       const TriRec *tris, int64_t nt, Pt4 *trn, hipStream_t s) {
   const int64_t npair = np > 0 ? (np + 2) / 2 : 0;
-  const int nbv = (int)std::min<int64_t>((npair + 255) / 256, derive_blocks());
+  const int nbv = (int)std::min<int64_t>((npair + 255) / 256, 8192);
   const int nbt = (int)std::min<int64_t>((nt + 255) / 256, 4096);
   if (nbv + nbt < 1) return;
   hipLaunchKernelGGL(k_bg_derive, dim3((unsigned)(nbv + nbt)), dim3(256), 0, s, xyz, np, g, xyzq, tris, nt, trn,
@@ -120,13 +115,6 @@ void launch_bg_derive(const double *xyz, int64_t np, GridDesc g, unsigned long l
 // any sampled tet of the cell is a valid start, the located tet does not
 // depend on the start (unique containing tet, or the canonical min-index tet
 // of a tie, see canonical_tet).
-// FROM_XYZ (run flag exp 15, A/B of the r04 verdict's "derive fused into
-// the hint build"): the four vertices' fixed-point coordinates computed here
-// from their double rows (the same quant_xyz, so the same cells) instead of
-// gathered from the derived xyzq array -- no separate pass over the vertices
-// V0 (run flag exp 16, A/B): the cell of the sample's first vertex instead
-// of its centroid -- one 8-B gather per sample instead of four; any tet of
-// the neighbourhood is a valid start (a longer walk at most)
 // the cell of a tet's centroid from its vertices' fixed-point coordinates
 __device__ __forceinline__ int64_t hint_cell(unsigned long long a, unsigned long long b, unsigned long long c,
                                              unsigned long long d, const GridDesc &g) {
@@ -142,89 +130,30 @@ __device__ __forceinline__ int64_t hint_cell(unsigned long long a, unsigned long
   return gcell(g, cq[0], cq[1], cq[2]);
 }
 
-template <bool PACKED, bool FROM_XYZ = false, bool V0 = false, int BS = 256>
-__global__ __launch_bounds__(BS) void k_hint_build(const int4 *__restrict__ packed, const int *__restrict__ kidx,
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_hint_build(const int4 *__restrict__ packed, const int *__restrict__ kidx,
                                                     const TetRec *__restrict__ tets, int64_t n,
                                                     int stride, int *__restrict__ grid, GridDesc g,
-                                                    const unsigned long long *__restrict__ xyzq,
-                                                    const double *__restrict__ xyz) {
+                                                    const unsigned long long *__restrict__ xyzq) {
   const int64_t t = xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
   if (t >= n) return;
   // the packed sample in cell order carries its tet indices (kidx)
   const int64_t k = (PACKED && kidx) ? (int64_t)kidx[t] : 1 + t * stride;
   const int4 v = PACKED ? packed[t] : *reinterpret_cast<const int4 *>(tets + k);
   if (v.x <= 0) return;
-  if constexpr (V0) {
-    const unsigned long long a = xyzq[v.x];
-    const unsigned long long M = (1ull << 21) - 1;
-    int cq[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ax++) cq[ax] = min((int)(((a >> (21 * ax)) & M) >> g.qf[ax]), g.dim[ax] - 1);
-    grid[gcell(g, cq[0], cq[1], cq[2])] = (int)k;
-    return;
-  }
-  unsigned long long a, b, c, d;
-  if constexpr (FROM_XYZ) {
-    a = quant_xyz(xyz + 3 * (int64_t)v.x, g);
-    b = quant_xyz(xyz + 3 * (int64_t)v.y, g);
-    c = quant_xyz(xyz + 3 * (int64_t)v.z, g);
-    d = quant_xyz(xyz + 3 * (int64_t)v.w, g);
-  } else {
-    a = xyzq[v.x]; b = xyzq[v.y]; c = xyzq[v.z]; d = xyzq[v.w];
-  }
-  grid[hint_cell(a, b, c, d, g)] = (int)k;
-}
-// PMX_HINT_FILT=1 (A/B, late r06): the same build with one grid store per
-// run of samples in one cell -- a lane whose left neighbour's sample falls in
-// its cell leaves the store to it (consecutive samples of a coherent
-// numbering share cells; any sample of the cell is a valid start, and the
-// left one is as good as the racy last writer)
-__global__ __launch_bounds__(256) void k_hint_build_filt(const int4 *__restrict__ packed, int64_t n, int stride,
-                                                         int *__restrict__ grid, GridDesc g,
-                                                         const unsigned long long *__restrict__ xyzq) {
-  const int64_t t = xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
-  const int64_t k = 1 + t * stride;
-  const int4 v = packed[t < n ? t : n - 1];
-  int64_t c = -1;
-  if (t < n && v.x > 0) c = hint_cell(xyzq[v.x], xyzq[v.y], xyzq[v.z], xyzq[v.w], g);
-  const long long cl = __shfl_up((long long)c, 1, 64);
-  if (c >= 0 && ((threadIdx.x & 63) == 0 || cl != (long long)c)) grid[c] = (int)k;
+  grid[hint_cell(xyzq[v.x], xyzq[v.y], xyzq[v.z], xyzq[v.w], g)] = (int)k;
 }
 void launch_hint_build(const int4 *packed, const int *kidx, const TetRec *tets, int64_t ne, int stride, int *grid,
-                       GridDesc g, const unsigned long long *xyzq, const double *xyz, hipStream_t s,
-                       bool v0, int bs, int64_t nsamp) {
+                       GridDesc g, const unsigned long long *xyzq, hipStream_t s, int64_t nsamp) {
   const int64_t n = nsamp >= 0 ? nsamp : (ne + stride - 1) / stride;   // nsamp < 0: every stride-th tet
   if (n < 1) return;
   const int64_t nb = (n + 255) / 256;
-  static const bool filt = [] {
-    const char *e = getenv("PMX_HINT_FILT");
-    return e && e[0] == '1';
-  }();
-  if (filt && packed && !kidx && xyzq && !v0 && bs == 256 && nsamp < 0 && n < INT32_MAX) {
-    hipLaunchKernelGGL(k_hint_build_filt, dim3((unsigned)nb), dim3(256), 0, s, packed, n, stride, grid, g, xyzq);
-    return;
-  }
-  if (v0 && xyzq && packed)
-    hipLaunchKernelGGL((k_hint_build<true, false, true>), dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n,
-                       stride, grid, g, xyzq, xyz);
-  else if (v0 && xyzq)
-    hipLaunchKernelGGL((k_hint_build<false, false, true>), dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n,
-                       stride, grid, g, xyzq, xyz);
-  else if (packed && !xyzq)
-    hipLaunchKernelGGL((k_hint_build<true, true>), dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n, stride,
-                       grid, g, xyzq, xyz);
-  else if (packed && bs == 1024)
-    hipLaunchKernelGGL((k_hint_build<true, false, false, 1024>), dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0,
-                       s, packed, kidx, tets, n, stride, grid, g, xyzq, xyz);
-  else if (packed && bs == 64)
-    hipLaunchKernelGGL((k_hint_build<true, false, false, 64>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s,
-                       packed, kidx, tets, n, stride, grid, g, xyzq, xyz);
-  else if (packed)
-    hipLaunchKernelGGL((k_hint_build<true, false>), dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n, stride,
-                       grid, g, xyzq, xyz);
+  if (packed)
+    hipLaunchKernelGGL(k_hint_build<true>, dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n, stride, grid,
+                       g, xyzq);
   else
-    hipLaunchKernelGGL((k_hint_build<false, false>), dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n, stride,
-                       grid, g, xyzq, xyz);
+    hipLaunchKernelGGL(k_hint_build<false>, dim3((unsigned)nb), dim3(256), 0, s, packed, kidx, tets, n, stride, grid,
+                       g, xyzq);
 }
 
 // The vertex-owner sample (r05): one tet per vertex -- the smallest tet
@@ -289,30 +218,6 @@ bool launch_owner_sample(const TetRec *tets, int64_t ne, int64_t np, unsigned *o
                      (const int *)flag, (const int *)pos, np, tets, out, kidx, d_count);
   if (hipMemcpyAsync(h_count, d_count, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) return false;
   return hipGetLastError() == hipSuccess;
-}
-
-// the hint cells with their start tet's compact record inline (run flag exp
-// 13, A/B of the r04 verdict's item 2a): cell c -> {k, w0, w1, w2},
-// {w3, w4, w5, 0}; the walk's first record comes with the cell (a read of
-// neighbouring cells) instead of a dependent gather of a random tet line
-__global__ __launch_bounds__(256) void k_hint_inline(const int *__restrict__ grid, int64_t cells,
-                                                     const WRec *__restrict__ wr, uint4 *__restrict__ hrec) {
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells;
-       c += (int64_t)gridDim.x * blockDim.x) {
-    const int k = grid[c];
-    uint4 a = make_uint4(0u, 0u, 0u, 0u), b = make_uint4(0u, 0u, 0u, 0u);
-    if (k) {
-      const WRec r = wr[k];
-      a = make_uint4((unsigned)k, r.w[0], r.w[1], r.w[2]);
-      b = make_uint4(r.w[3], r.w[4], r.w[5], 0u);
-    }
-    hrec[2 * c] = a;
-    hrec[2 * c + 1] = b;
-  }
-}
-void launch_hint_inline(const int *grid, int64_t cells, const WRec *wr, uint4 *hrec, hipStream_t s) {
-  const int64_t nb = std::min<int64_t>(std::max<int64_t>((cells + 255) / 256, 1), 65536);
-  hipLaunchKernelGGL(k_hint_inline, dim3((unsigned)nb), dim3(256), 0, s, grid, cells, wr, hrec);
 }
 
 // the walk's compact records (WRec, pmx_device.h) from the tet records, built
@@ -708,7 +613,7 @@ void launch_orphans(const uint8_t *mk, int64_t n, uint8_t keep, const OrphanRows
 // vertices its left neighbour -- the previous tet, which in any coherent
 // numbering shares most of them -- also holds (that lane stores them), and
 // each lane takes two tets per round (two loads in flight).
-// H tets per thread and iteration (loads in flight); PMX_MARK_TPT=4 (A/B)
+// H tets per thread and iteration (loads in flight)
 template <int H>
 __global__ __launch_bounds__(256) void k_mark_new_tets(const int4 *__restrict__ tv, int64_t ne,
                                                        uint8_t *__restrict__ mk) {
@@ -743,58 +648,6 @@ __global__ __launch_bounds__(256) void k_mark_new_tets(const int4 *__restrict__ 
     }
   }
 }
-// r06 (late): the same marks with the next round's tets loaded BEFORE this
-// round's byte stores, and every store issued (a buffer store whose offset is
-// out of the descriptor's range when it is filtered out: the hardware drops
-// it, no branch).  vmcnt counts loads and stores in one in-order counter on
-// gfx950, so k_mark_new_tets' loads, issued after the previous round's
-// stores, waited for those stores too (`s_waitcnt vmcnt(0)` at the loop
-// head); here the head waits vmcnt(4H): the stores stay in flight.
-template <int H>
-__global__ __launch_bounds__(256) void k_mark_new_tets_pipe(const int4 *__restrict__ tv, int64_t ne,
-                                                            uint8_t *__restrict__ mk, int nmk) {
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(mk, (short)0, nmk, 0x00020000);
-  const int64_t st = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nit = (ne + H * st - 1) / (H * st);    // uniform trip count (the shuffles below)
-  const bool lane0 = (threadIdx.x & 63) == 0;
-  const int64_t kb = 1 + H * (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int4 v[H];
-#pragma unroll
-  for (int h = 0; h < H; h++) v[h] = tv[min(kb + h * (int64_t)blockDim.x, ne)];
-  // 4H dropped stores (offset out of range): the loop is entered with the
-  // same VMEM pattern as its back edge (loads, then 4H stores), so the
-  // compiler's wait at the loop head is vmcnt(4H) on both paths, not 0
-#pragma unroll
-  for (int l = 0; l < 4 * H; l++) __builtin_amdgcn_raw_buffer_store_b8((unsigned char)1, rs, nmk + l * 64, 0, 0);
-  for (int64_t it = 0; it < nit; it++) {
-    const int64_t k0 = kb + H * it * st;
-    int4 a[H];
-#pragma unroll
-    for (int h = 0; h < H; h++) {
-      a[h] = v[h];
-      if (!(k0 + h * (int64_t)blockDim.x <= ne && a[h].x > 0)) a[h] = make_int4(0, 0, 0, 0);   // !MG_EOK / tail
-    }
-    // the next round's tets (clamped: the last round reloads row ne, unused)
-#pragma unroll
-    for (int h = 0; h < H; h++) v[h] = tv[min(k0 + H * st + h * (int64_t)blockDim.x, ne)];
-#pragma unroll
-    for (int h = 0; h < H; h++) {
-      const int4 q4 = a[h];
-      int4 u;
-      u.x = __shfl_up(q4.x, 1, 64); u.y = __shfl_up(q4.y, 1, 64);
-      u.z = __shfl_up(q4.z, 1, 64); u.w = __shfl_up(q4.w, 1, 64);
-      if (lane0) u = make_int4(0, 0, 0, 0);             // no left neighbour: store all
-      const int w[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-      for (int l = 0; l < 4; l++) {
-        const int q = w[l];
-        const bool keep = q > 0 && q != u.x && q != u.y && q != u.z && q != u.w;
-        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)1, rs, keep ? q - 1 : nmk, 0, 0);
-      }
-    }
-  }
-}
-
 // r06 (late): the marks deduplicated in LDS.  What bounds k_mark_new_tets is
 // not its 16-B tet stream but its byte stores: one L2 write request per lane
 // and vertex (≈ 1.5-2 per tet after the left-neighbour filter, a vertex is in
@@ -867,54 +720,17 @@ __global__ __launch_bounds__(256) void k_mark_new_tets_win(const int4 *__restric
   }
 }
 
+// the window kernel when the sizes allow (its word flush indexes in 32 bits),
+// else the plain marks
 void launch_mark_new_tets(const int4 *tv, int64_t ne, uint8_t *mk, int64_t nmk, hipStream_t s) {
-  // PMX_MARK_WIN=0 (A/B): the marks without the LDS window
-  static const bool winm = [] {
-    const char *e = getenv("PMX_MARK_WIN");
-    return !(e && e[0] == '0');
-  }();
-  // PMX_MARK_H=8 (A/B): 2048 tets per chunk instead of 1024
-  static const int wh = [] {
-    const char *e = getenv("PMX_MARK_H");
-    return e && e[0] == '8' ? 8 : 4;
-  }();
-  if (winm && ne >= 1 && nmk > 0 && nmk < INT32_MAX - MW_WIN) {
-    const int64_t nb = std::min<int64_t>((ne + 256 * wh - 1) / (256 * wh), 4096);
-    if (wh == 8)
-      hipLaunchKernelGGL(k_mark_new_tets_win<8>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk, nmk);
-    else
-      hipLaunchKernelGGL(k_mark_new_tets_win<4>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk, nmk);
-    return;
-  }
   if (ne < 1) return;
-  static const int tpt = [] {
-    const char *e = getenv("PMX_MARK_TPT");
-    return e && e[0] == '4' ? 4 : 2;
-  }();
-  // PMX_MARK_PIPE=1 (A/B): k_mark_new_tets_pipe (beside the derived data it
-  // takes memory bandwidth from them: C3 step 2.481-2.500 vs 2.470-2.488 ms)
-  static const bool pipe = [] {
-    const char *e = getenv("PMX_MARK_PIPE");
-    return e && e[0] == '1';
-  }();
-  // PMX_MARK_BLOCKS (A/B): the block cap -- the marks run beside the derived
-  // data and the hint build, which they slow by sharing the memory system
-  static const int64_t cap = [] {
-    const char *e = getenv("PMX_MARK_BLOCKS");
-    return e ? std::max<int64_t>(1, atoll(e)) : (int64_t)8192;
-  }();
-  const int64_t nb = std::min<int64_t>((ne + 256 * tpt - 1) / (256 * tpt), cap);
-  if (pipe && nmk > 0 && nmk < INT32_MAX - 4096) {
-    if (tpt == 4)
-      hipLaunchKernelGGL(k_mark_new_tets_pipe<4>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk, (int)nmk);
-    else
-      hipLaunchKernelGGL(k_mark_new_tets_pipe<2>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk, (int)nmk);
+  if (nmk > 0 && nmk < INT32_MAX - MW_WIN) {
+    const int64_t nb = std::min<int64_t>((ne + 256 * 4 - 1) / (256 * 4), 4096);
+    hipLaunchKernelGGL(k_mark_new_tets_win<4>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk, nmk);
     return;
   }
-  if (tpt == 4)
-    hipLaunchKernelGGL(k_mark_new_tets<4>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk);
-  else
-    hipLaunchKernelGGL(k_mark_new_tets<2>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk);
+  const int64_t nb = std::min<int64_t>((ne + 256 * 2 - 1) / (256 * 2), 8192);
+  hipLaunchKernelGGL(k_mark_new_tets<2>, dim3((unsigned)nb), dim3(256), 0, s, tv, ne, mk);
 }
 
 // ---- device residency across iterations (pmx_promote_background) ----------------

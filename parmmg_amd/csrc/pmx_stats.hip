@@ -403,10 +403,6 @@ __device__ __forceinline__ int pick_v(const TetRec &t, int l) {
   return (t.v[0] & -(int)(l == 0)) | (t.v[1] & -(int)(l == 1)) | (t.v[2] & -(int)(l == 2)) |
          (t.v[3] & -(int)(l == 3));
 }
-__device__ __forceinline__ int pick_nb(const TetRec &t, int l) {
-  return (t.nb[0] & -(int)(l == 0)) | (t.nb[1] & -(int)(l == 1)) | (t.nb[2] & -(int)(l == 2)) |
-         (t.nb[3] & -(int)(l == 3));
-}
 
 
 // log1p as glibc computes it (sysdeps/ieee754/dbl-64/s_log1p.c: Sun's fdlibm
@@ -490,13 +486,11 @@ __device__ __forceinline__ IsoEdge iso_edge_load(const StatArgs &A, int p1, int 
   __builtin_amdgcn_sched_barrier(0);
   return e;
 }
-template <bool TWO = false>   // TWO (A/B): the two-branch form, two divisions in a mixed wave
 __device__ __forceinline__ double iso_edge_len(const IsoEdge &e) {
   double ux = e.c2.x - e.c1.x, uy = e.c2.y - e.c1.y, uz = e.c2.z - e.c1.z;
   double l = ux * ux + uy * uy + uz * uz;
   l = sqrt(l);
   double r = e.h2 / e.h1 - 1.0;
-  if constexpr (TWO) return (fabs(r) < PMX_EPS) ? (l / e.h1) : (l / (e.h2 - e.h1) * pmx_log1p(r));
   // one division for both branches (l / h1 or l / (h2 - h1): the same
   // correctly rounded quotients as the two-branch form, one instead of two
   // in a wave whose lanes take both)
@@ -508,7 +502,7 @@ __device__ __forceinline__ double iso_edge_len(const IsoEdge &e) {
 // MMG5_lenEdg_iso / lenEdg33_ani (restated, unpinned; the surface lengths
 // MMG5_lenSurfEdg_iso / lenSurfEdg33_ani of the parallel edges take the same
 // formulas in classic metric storage)
-template <bool ANI, bool TWO = false>
+template <bool ANI>
 __device__ __forceinline__ double edge_len_t(const StatArgs &A, int p1, int p2) {
   if (ANI) {
     D3 c1 = sld3(A, p1), c2 = sld3(A, p2);
@@ -521,7 +515,7 @@ __device__ __forceinline__ double edge_len_t(const StatArgs &A, int p1, int p2) 
     return (sqrt(dd1) + sqrt(dd2) + 4.0 * sqrt(0.5 * (dd1 + dd2))) / 6.0;
   }
   const IsoEdge e = iso_edge_load(A, p1, p2);
-  return iso_edge_len<TWO>(e);
+  return iso_edge_len(e);
 }
 __device__ double edge_len(const StatArgs &A, int p1, int p2) {
   return A.msize == 6 ? edge_len_t<true>(A, p1, p2) : edge_len_t<false>(A, p1, p2);
@@ -872,19 +866,6 @@ __device__ __forceinline__ TetRec shell_rec(const StatArgs &A, const TetRec (*sr
   return TetRec{{lv.x, lv.y, lv.z, lv.w}, {ln.x, ln.y, ln.z, ln.w}};
 }
 
-// A shell record from HBM / L2, unconditionally (index 0: the unused slot
-// 0).  No LDS path and no select on the loaded value: with either, the
-// compiler turns the load into a branch (a select of a single-use load
-// becomes a branch), and a conditional load makes it wait for every load in
-// flight at the next join -- here the number of loads in flight is the same
-// on every path, so the length's arithmetic overlaps the second step's
-// records.
-__device__ __forceinline__ TetRec shell_rec_g(const StatArgs &A, int c) {
-  const int4 *g = reinterpret_cast<const int4 *>(A.tets) + 2 * (int64_t)c;
-  const int4 gv = g[0], gn = g[1];
-  return TetRec{{gv.x, gv.y, gv.z, gv.w}, {gn.x, gn.y, gn.z, gn.w}};
-}
-
 // True iff no admissible tet with index < k contains the edge (a, b) of tet
 // k.  The shell is rotated from k through the two faces of k that contain the
 // edge (cursors c0, c1; keep0/keep1 = the vertex of the face just crossed),
@@ -939,11 +920,10 @@ __device__ __forceinline__ bool owns_edge(const StatArgs &A, const TetRec (*srec
 // returns become a "decided" mask, so the wave issues no branch per check.
 // The steps are separate calls so that the caller can put work between them:
 // k_prilen evaluates the edge's length while the second step's records load.
-template <bool L, bool G>
+template <bool L>
 struct FlatRot {
   int c0, c1, keep0, keep1;
   TetRec r0, r1;
-  int i0, i1;                                      // where r0 / r1 were loaded from
   bool done = false, own = true;
   __device__ __forceinline__ void step(const StatArgs &A, const TetRec (*srec)[256], long long kb0, long long kb1,
                                        int64_t k64, int a, int b) {
@@ -967,16 +947,8 @@ struct FlatRot {
     const bool d_small2 = (need0 && c0 < k) || (need1 && c1 < k);
     own = done ? own : !d_small2;
     done = done || d_small2 || (need0 && c0 == c1);
-    if constexpr (G) {
-      // a record not needed is reloaded from where it came (same value)
-      i0 = (!done && need0) ? c0 : i0;
-      i1 = (!done && need1) ? c1 : i1;
-      r0 = shell_rec_g(A, i0);
-      r1 = shell_rec_g(A, i1);
-    } else {
-      if (!done && need0) r0 = shell_rec<L>(A, srec, kb0, kb1, c0);
-      if (!done && need1) r1 = shell_rec<L>(A, srec, kb0, kb1, c1);
-    }
+    if (!done && need0) r0 = shell_rec<L>(A, srec, kb0, kb1, c0);
+    if (!done && need1) r1 = shell_rec<L>(A, srec, kb0, kb1, c1);
   }
   __device__ __forceinline__ bool finish(const StatArgs &A, const TetRec (*srec)[256], long long kb0, long long kb1,
                                          int64_t k64, int a, int b) {
@@ -1004,12 +976,7 @@ struct FlatRot {
 #define LEN_QCAP 2048                 // > 255 left over + 6 * 256 queued
 // SURF (tensor metrics with surface data or ridge storage): every length by
 // len_tet_ani from the owner tet's xTetra edge tags and vertices.
-// X (measurement only, PMX_PRILEN_EXP): bits 0-1 with PMX_EXPERIMENTS=1 give
-// wrong results by design -- bit 0 no length evaluation (1.0), bit 1 no shell
-// rotation (every candidate counts), the VALU breakdown of the r05 verdict's
-// item 6; bit 2 (4: same results) the rotation as owns_edge's loop from the
-// first step instead of owns_edge_flat (r05's kernel, for the A/B).
-template <bool ANI, bool TAGS, bool PAR, int W = 1, bool L = false, bool SURF = false, int X = 0>
+template <bool ANI, bool TAGS, bool PAR, int W = 1, bool L = false, bool SURF = false>
 __global__ __launch_bounds__(256, W) void k_prilen(StatArgs A, LenPart *parts) {
   __shared__ TetRec srec[2][256];
   __shared__ unsigned short q[LEN_QCAP + 2];     // + the spare entry of unset slots
@@ -1018,38 +985,15 @@ __global__ __launch_bounds__(256, W) void k_prilen(StatArgs A, LenPart *parts) {
   __shared__ unsigned lcnt[10];
   LenAcc acc(lcnt);
   // The tets a workgroup takes, batch by batch (kb = first tet of a batch,
-  // valid while kb <= k1):
-  //  * contiguous (sched_chunk 0): XCD-contiguous ranges, one per workgroup;
-  //    the shells and points of the next z-layer of cells are another
-  //    range's, read by the same L2;
-  //  * front (sched_chunk C): each XCD's eighth of the tets is dealt out in
-  //    chunks of C batches, round-robin over the XCD's co-resident
-  //    workgroups, so the XCD works on one contiguous window that moves
-  //    forward: a +y shell (a few batches ahead) is a batch another
-  //    workgroup of the same L2 loads about then.
-  // Either way a workgroup's batches come in increasing tet order (the ring's
-  // keys stay ordered).
+  // valid while kb <= k1): XCD-contiguous ranges, one per workgroup, in
+  // increasing tet order (the ring's keys stay ordered); the shells and
+  // points of the next z-layer of cells are another range's, read by the
+  // same L2.
   const unsigned tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int64_t C = A.sched_chunk;
-  int64_t lb, k0, k1, jump = 0, xlo = 1;
-  if (C == 0) {
-    lb = xcd_remap(blockIdx.x, gridDim.x);
-    const int64_t per = (A.ne + gridDim.x - 1) / gridDim.x;
-    k0 = 1 + lb * per;
-    k1 = min(A.ne, k0 + per - 1);
-  } else {
-    lb = blockIdx.x;
-    const int64_t x = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int64_t G = ((int64_t)gridDim.x - x + 7) >> 3;     // this XCD's workgroups
-    xlo = 1 + x * A.ne / 8;
-    k1 = (x + 1) * A.ne / 8;
-    k0 = xlo + j * C * 256;
-    jump = (G - 1) * C * 256;
-  }
-  auto next_batch = [&](int64_t kb) -> int64_t {
-    if (C == 0) return kb + 256;
-    return kb + 256 + (((kb - xlo) >> 8) % C == C - 1 ? jump : 0);
-  };
+  const int64_t lb = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t per = (A.ne + gridDim.x - 1) / gridDim.x;
+  const int64_t k0 = 1 + lb * per;
+  const int64_t k1 = min(A.ne, k0 + per - 1);
   unsigned head = 0, tail = 0;                   // ring positions (uniform)
   // each batch's records go to an LDS buffer; the next batch's are loaded at
   // the start of the batch and written to the other buffer after its rounds,
@@ -1071,7 +1015,7 @@ __global__ __launch_bounds__(256, W) void k_prilen(StatArgs A, LenPart *parts) {
     const bool more = kb <= k1;
     if (!more && head == tail) break;
     const unsigned prev_end = tail;              // entries before it: the previous batch
-    const int64_t kbn = next_batch(kb);
+    const int64_t kbn = kb + 256;
     const int64_t kn = max<int64_t>(1, min(kbn + (int64_t)tid, A.ne));
     const int4 pv = recs[2 * kn], pn = recs[2 * kn + 1];
     if (more) {
@@ -1153,36 +1097,19 @@ __global__ __launch_bounds__(256, W) void k_prilen(StatArgs A, LenPart *parts) {
         // the first rotation step's records, issued with the points' loads
         TetRec r0{}, r1{};
         // FLAT: the rotation's first two steps as straight-line selects (no
-        // point tags); GREC (X bit 3): the flat steps' records always from
-        // HBM / L2, no LDS path; EARLY (X bit 4): the first step before the
-        // length (its records wanted first), the second step's loads in flight
-        // during the length's arithmetic
-        constexpr bool FLAT = !(X & 6) && !TAGS;
-        constexpr bool GREC = FLAT && (X & 8);
-        constexpr bool EARLY = FLAT && (X & 16) && !ANI && !SURF && !(X & 1);
-        if constexpr (GREC) {
-          r0 = shell_rec_g(A, c0);
-          r1 = shell_rec_g(A, c1);
-        } else if constexpr (!(X & 2)) {
-          if (c0) r0 = shell_rec<L>(A, srec, kb0, kb1, c0);
-          if (c1) r1 = shell_rec<L>(A, srec, kb0, kb1, c1);
-        }
-        FlatRot<L, GREC> fr{c0, c1, keep0, keep1, r0, r1, c0, c1};
-        if constexpr (EARLY) {
-          const IsoEdge e = iso_edge_load(A, a, b);   // in flight during the step
-          fr.step(A, srec, kb0, kb1, kk, a, b);
-          len = iso_edge_len(e);
-        } else if constexpr (SURF) {
+        // point tags)
+        constexpr bool FLAT = !TAGS;
+        if (c0) r0 = shell_rec<L>(A, srec, kb0, kb1, c0);
+        if (c1) r1 = shell_rec<L>(A, srec, kb0, kb1, c1);
+        FlatRot<L> fr{c0, c1, keep0, keep1, r0, r1};
+        if constexpr (SURF) {
           const int vv[4] = {sv[0], sv[1], sv[2], sv[3]};
           len = len_tet_ani(A, vv, ia, a, b, A.etag ? (unsigned)A.etag[kk] : 0u);
-        } else if constexpr (X & 1) {
-          len = 1.0 + 1e-9 * (double)(a & 7);
         } else {
-          len = edge_len_t<ANI, (X & 128) != 0>(A, a, b);
+          len = edge_len_t<ANI>(A, a, b);
         }
-        if constexpr (X & 2) on = true;
-        else if constexpr (FLAT) {
-          if constexpr (!EARLY) fr.step(A, srec, kb0, kb1, kk, a, b);
+        if constexpr (FLAT) {
+          fr.step(A, srec, kb0, kb1, kk, a, b);
           fr.step(A, srec, kb0, kb1, kk, a, b);
           on = fr.finish(A, srec, kb0, kb1, kk, a, b) && !(PAR && par_excluded(A, a, b));
         } else
@@ -1204,119 +1131,6 @@ __global__ __launch_bounds__(256, W) void k_prilen(StatArgs A, LenPart *parts) {
     }
     __syncthreads();                             // srec, wcnt, kbase rewritten next
     kb = kbn;
-  }
-  acc.store(parts + lb);
-}
-
-// ---- prilen, edge-bucket variant (A/B of the shell rotation) --------------------
-//
-// The r04 verdict's alternative to the rotation: unique edges through buckets
-// of the smaller endpoint instead of shell walks.  The face-neighbour filter
-// of k_prilen keeps the candidates (a tet's edge no smaller face neighbour
-// disowns: 1.0015 per unique edge on Kuhn meshes); each candidate goes to the
-// bucket of its smaller endpoint (counts and placement aggregated per
-// workgroup in an LDS hash, one global atomic per distinct bucket -- the
-// LDS-aggregated bucketing of pmx_topo.hip); an edge's owner is its candidate
-// with the smallest key 6 k + ia in the bucket (the reference's first
-// occurrence), found by scanning the bucket.  Point tags (the 4-ridge
-// filter disables the face filter) and the surface-aware tensor lengths keep
-// the rotation.  Selected by PMX_PRILEN_BUCKETS=1.
-#define PB_HT 2048
-__device__ __forceinline__ int pb_slot(int *keys, int a) {
-  unsigned h = ((unsigned)a * 2654435761u) >> (32 - 11);
-  for (;;) {
-    const int old = atomicCAS(&keys[h], -1, a);
-    if (old == -1 || old == a) return (int)h;
-    h = (h + 1) & (PB_HT - 1);
-  }
-}
-// the candidate edges of tet k (bit ia): valid tet, no smaller face neighbour
-// on either face containing the edge
-__device__ __forceinline__ unsigned pb_cands(const TetRec &t, int64_t k) {
-  unsigned m = 0;
-  if (t.v[0] <= 0) return 0;
-#pragma unroll
-  for (int ia = 0; ia < 6; ia++) {
-    const int n0 = pick_nb(t, oth0(ia)), n1 = pick_nb(t, oth1(ia));
-    if ((n0 && n0 < k) || (n1 && n1 < k)) continue;
-    m |= 1u << ia;
-  }
-  return m;
-}
-// PASS 0 counts, PASS 1 places: records {a, b, 6 k + ia, 0} in the reference's
-// orientation (a = v[IARE[ia][0]]), bucket = min(a, b)
-template <int PASS>
-__global__ __launch_bounds__(256) void k_pb_bucket(const TetRec *__restrict__ tets, int64_t ne,
-                                                   unsigned *__restrict__ cnt, int4 *__restrict__ rec) {
-  __shared__ int keys[PB_HT];
-  __shared__ unsigned cnts[PB_HT];
-  for (int i = threadIdx.x; i < PB_HT; i += blockDim.x) { keys[i] = -1; cnts[i] = 0u; }
-  __syncthreads();
-  const int64_t k = xcd_remap(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x + 1;
-  TetRec t{};
-  unsigned m = 0;
-  int slot[6];
-  unsigned rank[6];
-  if (k <= ne) {
-    t = tets[k];
-    m = pb_cands(t, k);
-#pragma unroll
-    for (int ia = 0; ia < 6; ia++) {
-      slot[ia] = 0;
-      rank[ia] = 0;
-      if (!((m >> ia) & 1u)) continue;
-      const int a = pick_v(t, iare0(ia)), b = pick_v(t, iare1(ia));
-      slot[ia] = pb_slot(keys, min(a, b));
-      rank[ia] = atomicAdd(&cnts[slot[ia]], 1u);
-    }
-  }
-  __syncthreads();
-  if (PASS == 0) {
-    for (int i = threadIdx.x; i < PB_HT; i += blockDim.x)
-      if (keys[i] >= 0) atomicAdd(cnt + keys[i], cnts[i]);
-    return;
-  }
-  // one reservation per bucket: the workgroup's run starts there
-  for (int i = threadIdx.x; i < PB_HT; i += blockDim.x)
-    if (keys[i] >= 0) cnts[i] = atomicAdd(cnt + keys[i], cnts[i]);
-  __syncthreads();
-#pragma unroll
-  for (int ia = 0; ia < 6; ia++) {
-    if (!((m >> ia) & 1u)) continue;
-    const int a = pick_v(t, iare0(ia)), b = pick_v(t, iare1(ia));
-    rec[cnts[slot[ia]] + rank[ia]] = make_int4(a, b, (int)(6u * (unsigned)k + (unsigned)ia), 0);
-  }
-}
-// one thread per candidate: the owner (smallest key among the bucket's
-// candidates of the same edge) measures it
-template <bool ANI, bool PAR>
-__global__ __launch_bounds__(256) void k_pb_edges(StatArgs A, const int4 *__restrict__ rec, int64_t nrec,
-                                                  const unsigned *__restrict__ off, LenPart *parts) {
-  __shared__ unsigned lcnt[10];
-  LenAcc acc(lcnt);
-  const int64_t lb = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t per = ((nrec + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;
-  const int64_t r0 = lb * per, r1 = min(nrec, r0 + per);
-  for (int64_t rb = r0; rb < r0 + per; rb += blockDim.x) {   // uniform trip count
-    const int64_t r = rb + threadIdx.x;
-    bool on = false;
-    double len = 0.0;
-    long long key = 0;
-    if (r < r1) {
-      const int4 e = rec[r];
-      const int lo = min(e.x, e.y), hi = max(e.x, e.y);
-      const unsigned me = (unsigned)e.z;
-      const unsigned b0 = off[lo], b1 = off[lo + 1];
-      bool own = true;
-      for (unsigned q = b0; q < b1; q++) {
-        const int4 o = rec[q];
-        own = own && !(max(o.x, o.y) == hi && (unsigned)o.z < me);
-      }
-      on = own && !(PAR && par_excluded(A, e.x, e.y));
-      if (on) len = edge_len_t<ANI>(A, e.x, e.y);
-      key = LEN_STEP2 + (long long)me;
-    }
-    acc.add(on, len, key);
   }
   acc.store(parts + lb);
 }
@@ -1944,12 +1758,6 @@ int pmx_prilen_device(pmx_ctx *ctx, int metRidTyp, const pmx_par_edges *par, voi
       ppt[(size_t)(key & 0xffffffffu)] = 1;
     }
   }
-  // the schedule (PMX_PRILEN_SCHED=C: the moving front in chunks of C
-  // batches, grid = the co-resident workgroups; unset: contiguous ranges)
-  static const int sched = [] {
-    const char *e = getenv("PMX_PRILEN_SCHED");
-    return e ? std::max(0, atoi(e)) : 0;
-  }();
   using KFn = void (*)(StatArgs, LenPart *);
   // variants: metric kind x point tags x parallel edges (each drops the
   // other paths' registers and branches)
@@ -1966,97 +1774,23 @@ int pmx_prilen_device(pmx_ctx *ctx, int metRidTyp, const pmx_par_edges *par, voi
       k_prilen<true, false, false, 1, true>,   k_prilen<true, false, true, 1, true>,
       k_prilen<true, true, false, 1, true>,    k_prilen<true, true, true, 1, true>};
   // lean 32-bit index arithmetic while 6 ne + 5 fits 32 bits (PMX_PRILEN_WIDE=1:
-  // the 64-bit variant, for the A/B)
+  // the 64-bit variant whatever the size)
   static const bool wide = getenv("PMX_PRILEN_WIDE") != nullptr;
   const bool lean = !wide && A.ne < 700000000LL;
   const int sel = (lean ? 8 : 0) | (ani ? 4 : 0) | (A.ptag ? 2 : 0) |
                   (par && par->n > 0 && !excl.empty() ? 1 : 0);
   // tensor metrics measured along the surface / in ridge storage
   // (len_tet_ani): the owner tet's xTetra tags and vertices per edge
+  // (held to 4 waves per SIMD: they sit at the 128-VGPR edge, where the
+  // compiler's own choice falls on either side of it)
   static const KFn kfs[8] = {
-      k_prilen<true, false, false, 1, false, true>, k_prilen<true, false, true, 1, false, true>,
-      k_prilen<true, true, false, 1, false, true>,  k_prilen<true, true, true, 1, false, true>,
-      k_prilen<true, false, false, 1, true, true>,  k_prilen<true, false, true, 1, true, true>,
-      k_prilen<true, true, false, 1, true, true>,   k_prilen<true, true, true, 1, true, true>};
+      k_prilen<true, false, false, 4, false, true>, k_prilen<true, false, true, 4, false, true>,
+      k_prilen<true, true, false, 4, false, true>,  k_prilen<true, true, true, 4, false, true>,
+      k_prilen<true, false, false, 4, true, true>,  k_prilen<true, false, true, 4, true, true>,
+      k_prilen<true, true, false, 4, true, true>,   k_prilen<true, true, true, 4, true, true>};
   const bool surf = ani && (ctx->have_surf || A.ridmet);
-  KFn kern = surf ? kfs[(lean ? 4 : 0) | (sel & 3)] : kfn[sel];
-  // measurement variants of the default iso kernel: PMX_PRILEN_EXP=1..3 with
-  // PMX_EXPERIMENTS=1 (results wrong by design: the VALU breakdown), 4 the r05
-  // rotation loop, 8 / 16 / 24 the flat rotation's record and order variants,
-  // 32 / 33 the default at 6 / 4 waves per SIMD (same results)
-  {
-    static const int xp = [] {
-      const char *e = getenv("PMX_PRILEN_EXP"), *x = getenv("PMX_EXPERIMENTS");
-      const int v = e ? atoi(e) : 0;
-      if (v == 4 || v == 8 || v == 16 || v == 24 || v == 32 || v == 33 || v == 128) return v;
-      return (e && x && x[0] == '1') ? std::max(0, std::min(3, v)) : 0;
-    }();
-    KFn kv = nullptr;
-    switch (xp) {
-      case 1: kv = k_prilen<false, false, false, 5, true, false, 1>; break;
-      case 2: kv = k_prilen<false, false, false, 5, true, false, 2>; break;
-      case 3: kv = k_prilen<false, false, false, 5, true, false, 3>; break;
-      case 4: kv = k_prilen<false, false, false, 5, true, false, 4>; break;
-      case 8: kv = k_prilen<false, false, false, 5, true, false, 8>; break;
-      case 16: kv = k_prilen<false, false, false, 5, true, false, 16>; break;
-      case 24: kv = k_prilen<false, false, false, 5, true, false, 24>; break;
-      case 32: kv = k_prilen<false, false, false, 6, true, false, 0>; break;    // 6 waves / SIMD
-      case 33: kv = k_prilen<false, false, false, 4, true, false, 0>; break;    // 4 waves / SIMD
-      case 128: kv = k_prilen<false, false, false, 5, true, false, 128>; break; // two-division length
-      default: break;
-    }
-    if (kv && sel == 8 && !surf) kern = kv;
-  }
-  int nb = stat_blocks(ctx->ne);
-  A.sched_chunk = 0;
-  if (sched > 0) {
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess ||
-        per_cu < 1 || cus < 8) {
-      ctx->err = "pmx_prilen: occupancy query";
-      return 0;
-    }
-    nb = per_cu * cus / 8 * 8;
-    A.sched_chunk = sched;
-  }
-  // the edge-bucket variant (A/B): no point tags, no surface-aware tensor path
-  static const bool buckets = [] {
-    const char *e = getenv("PMX_PRILEN_BUCKETS");
-    return e && e[0] == '1';
-  }();
-  const bool use_pb = buckets && !A.ptag && !surf;
-  int64_t npb = 0;
-  if (use_pb) {
-    const int64_t np = ctx->np;
-    if (!pmx_dgrow(ctx, ctx->d_pbcnt, (size_t)(np + 2)) || !pmx_dgrow(ctx, ctx->d_pboff, (size_t)(np + 2)))
-      return 0;
-    size_t tb = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ctx->d_pbcnt.p, ctx->d_pboff.p, (int)(np + 2), s);
-    if (!pmx_dgrow(ctx, ctx->d_pbtmp, tb)) return 0;
-    const unsigned nbt = (unsigned)std::max<int64_t>((ctx->ne + 255) / 256, 1);
-    if (hipMemsetAsync(ctx->d_pbcnt.p, 0, (size_t)(np + 2) * sizeof(unsigned), s) != hipSuccess) return 0;
-    hipLaunchKernelGGL(k_pb_bucket<0>, dim3(nbt), dim3(256), 0, s, (const TetRec *)ctx->d_tets.p, ctx->ne,
-                       ctx->d_pbcnt.p, (int4 *)nullptr);
-    if (hipcub::DeviceScan::ExclusiveSum(ctx->d_pbtmp.p, tb, ctx->d_pbcnt.p, ctx->d_pboff.p, (int)(np + 2), s) !=
-        hipSuccess) {
-      ctx->err = "pmx_prilen: bucket scan";
-      return 0;
-    }
-    unsigned tot = 0;
-    if (hipMemcpyAsync(&tot, ctx->d_pboff.p + np + 1, sizeof tot, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      ctx->err = "pmx_prilen: bucket total";
-      return 0;
-    }
-    npb = tot;
-    if (!pmx_dgrow(ctx, ctx->d_pbrec, (size_t)std::max<int64_t>(npb, 1)) ||
-        hipMemcpyAsync(ctx->d_pbcnt.p, ctx->d_pboff.p, (size_t)(np + 2) * sizeof(unsigned), hipMemcpyDeviceToDevice,
-                       s) != hipSuccess)
-      return 0;
-    hipLaunchKernelGGL(k_pb_bucket<1>, dim3(nbt), dim3(256), 0, s, (const TetRec *)ctx->d_tets.p, ctx->ne,
-                       ctx->d_pbcnt.p, ctx->d_pbrec.p);
-  }
+  const KFn kern = surf ? kfs[(lean ? 4 : 0) | (sel & 3)] : kfn[sel];
+  const int nb = stat_blocks(ctx->ne);
   if (!ensure_red(ctx, sizeof(LenPart) * ((size_t)nb + 1 + FINAL_GRID + 1))) return 0;
   LenPart *parts = (LenPart *)ctx->d_red.p;
   A.npar = (int64_t)excl.size();
@@ -2083,15 +1817,7 @@ int pmx_prilen_device(pmx_ctx *ctx, int metRidTyp, const pmx_par_edges *par, voi
   else
     hipLaunchKernelGGL(k_prilen_par, dim3(1), dim3(256), 0, s, A, (const int2 *)nullptr, (const uint16_t *)nullptr,
                        (int64_t)0, parts);
-  if (use_pb) {
-    using KP = void (*)(StatArgs, const int4 *, int64_t, const unsigned *, LenPart *);
-    static const KP kp[2][2] = {{k_pb_edges<false, false>, k_pb_edges<false, true>},
-                                {k_pb_edges<true, false>, k_pb_edges<true, true>}};
-    hipLaunchKernelGGL(kp[ani ? 1 : 0][A.npar ? 1 : 0], dim3(nb), dim3(256), 0, s, A, (const int4 *)ctx->d_pbrec.p,
-                       npb, (const unsigned *)ctx->d_pboff.p, parts + 1);
-  } else {
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, s, A, parts + 1);
-  }
+  hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, s, A, parts + 1);
   LenPart *mid = parts + 1 + nb;
   hipLaunchKernelGGL(k_prilen_final, dim3(FINAL_GRID), dim3(256), 0, s, parts, nb + 1, mid,
                      (pmx_len_part *)nullptr, ctx->d_tets.p, (const int2 *)ctx->d_pedge.p);

@@ -25,7 +25,6 @@
 #include <vector>
 #include "pmx_internal.h"
 
-static unsigned nblk_(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
 
 // MMG5_idir: local vertices of face f (opposite vertex f), outward order
 __constant__ int TOPO_IDIR[4][3] = {{1, 2, 3}, {0, 3, 2}, {0, 1, 3}, {0, 2, 1}};
@@ -120,31 +119,13 @@ __global__ __launch_bounds__(256) void k_face_scatter(const int4 *__restrict__ t
   }
 }
 
-// one thread per record: its partner in the bucket of its smallest vertex
-__global__ __launch_bounds__(256) void k_face_match(const int4 *__restrict__ rec, int64_t nb,
-                                                    const unsigned *__restrict__ off,
-                                                    int *__restrict__ adja,
-                                                    unsigned *__restrict__ nbad) {
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= (int64_t)off[nb]) return;                // records of valid tets only
-  const int4 me = rec[s];
-  const unsigned lo = off[me.x], hi = off[me.x + 1];
-  int partner = 0, n = 0;
-  for (unsigned r = lo; r < hi; r++) {
-    const int4 o = rec[r];
-    if (r != (unsigned)s && o.y == me.y && o.z == me.z) { partner = o.w; n++; }
-  }
-  adja[me.w - 3] = (n == 1) ? partner : 0;       // 4*(k-1)+1+f = owner - 3
-  if (n > 1) atomicAdd(nbad, 1u);
-}
-
-// The same matching with the records staged in LDS: a workgroup owns
-// MATCH_R consecutive records and loads them with MATCH_PAD records on either
-// side (coalesced, 16 KB); a record whose bucket lies inside that window is
-// compared against the LDS copy, any other (a bucket longer than the pads)
-// against global memory.  One global read per record and window instead of
-// one per (record, bucket member): the global-scan variant re-reads every
-// bucket once per member (~24 x 16 B per record).
+// One thread per record: its partner in the bucket of its smallest vertex,
+// with the records staged in LDS.  A workgroup owns MATCH_R consecutive
+// records and loads them with MATCH_PAD records on either side (coalesced,
+// 16 KB); a record whose bucket lies inside that window is compared against
+// the LDS copy, any other (a bucket longer than the pads) against global
+// memory: one global read per record and window instead of one per (record,
+// bucket member), ~24 x 16 B per record.
 #define MATCH_R 512
 #define MATCH_PAD 256
 __global__ __launch_bounds__(256) void k_face_match_lds(const int4 *__restrict__ rec, int64_t nb,
@@ -182,21 +163,10 @@ __global__ __launch_bounds__(256) void k_face_match_lds(const int4 *__restrict__
   }
 }
 
-// PMX_TOPO_MATCH=global: the global-scan matching, for the A/B
-static bool topo_match_global() {
-  static const bool g = [] {
-    const char *e = getenv("PMX_TOPO_MATCH");
-    return e && std::string(e) == "global";
-  }();
-  return g;
-}
 static void launch_face_match(const int4 *rec, int64_t ne, int64_t np, const unsigned *off, int *dadja,
                               unsigned *nbad, hipStream_t s) {
-  if (topo_match_global())
-    hipLaunchKernelGGL(k_face_match, dim3(nblk_(4 * ne)), dim3(256), 0, s, rec, np + 1, off, dadja, nbad);
-  else
-    hipLaunchKernelGGL(k_face_match_lds, dim3((unsigned)std::max<int64_t>((4 * ne + MATCH_R - 1) / MATCH_R, 1)),
-                       dim3(256), 0, s, rec, np + 1, off, dadja, nbad);
+  hipLaunchKernelGGL(k_face_match_lds, dim3((unsigned)std::max<int64_t>((4 * ne + MATCH_R - 1) / MATCH_R, 1)),
+                     dim3(256), 0, s, rec, np + 1, off, dadja, nbad);
 }
 
 // ---- boundary trias and their edge adjacency -------------------------------------

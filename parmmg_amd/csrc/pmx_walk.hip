@@ -184,37 +184,10 @@ __device__ __forceinline__ void walk_finish(const VolArgs &A, int64_t i, D3 p, b
     }
     A.elem[i] = cur;
     const int v[4] = {t.v[0], t.v[1], t.v[2], t.v[3]};
-    if (A.exp == 14) {
-      // measurement (r04 verdict item 2b): status, write mask and steps in
-      // one 4-B word -- two stores fewer per point (not decoded downstream)
-      const unsigned wm = interp_layout<LAYOUT, S>(A.sol, A.sd, v, lam, A.out + i * A.sd.S);
-      A.status[i] = (int)(1u | ((wm | A.const_bit) << 2) | ((unsigned)step << 10));
-    } else if (A.exp == 24) {
-      // A/B (r06): the results stored non-temporally (streamed past L2, which
-      // keeps the records and vertex rows other walks reuse)
-      __builtin_nontemporal_store(cur, A.elem + i);
-      __builtin_nontemporal_store(1, A.status + i);
-      __builtin_nontemporal_store(step, A.steps + i);
-      unsigned wm;
-      if constexpr (LAYOUT == LAYOUT_ISO || LAYOUT == LAYOUT_ANI) {
-        constexpr int NO = LAYOUT == LAYOUT_ANI ? 6 : (S > 0 ? S : 1);
-        double o[NO];
-        wm = interp_layout<LAYOUT, S>(A.sol, A.sd, v, lam, o);
-        if (wm) {                                  // (a failed inversion leaves the row untouched)
-#pragma unroll
-          for (int j = 0; j < NO; j++) __builtin_nontemporal_store(o[j], A.out + i * A.sd.S + j);
-        }
-      } else {
-        wm = interp_layout<LAYOUT, S>(A.sol, A.sd, v, lam, A.out + i * A.sd.S);
-      }
-      __builtin_nontemporal_store((uint8_t)(wm | A.const_bit), A.wmask + i);
-    } else {
-      A.status[i] = 1;
-      A.steps[i] = step;
-      if (A.exp == 4) return;                      // measurement: no interpolation
-      unsigned wm = interp_layout<LAYOUT, S>(A.sol, A.sd, v, lam, A.out + i * A.sd.S);
-      A.wmask[i] = (uint8_t)(wm | A.const_bit);
-    }
+    A.status[i] = 1;
+    A.steps[i] = step;
+    unsigned wm = interp_layout<LAYOUT, S>(A.sol, A.sd, v, lam, A.out + i * A.sd.S);
+    A.wmask[i] = (uint8_t)(wm | A.const_bit);
     s_cnt += 1; s_sum += step;
     s_max = max(s_max, (unsigned)step); s_min = min(s_min, (unsigned)step);
   } else {
@@ -375,8 +348,8 @@ __device__ __forceinline__ int exact_next(const TetRec &t, const double lam[4], 
 }
 
 // the walk's tet record: through the compact copy (CW) or the full record
-// (whole: exp 17, A/B of the per-field escapes -- a record with a far field
-// is read whole from the 32-B records, the r04 rule)
+// (whole: run-flag experiment 17 -- a record with a far field is read whole
+// from the 32-B records instead of resolving the chosen field)
 template <bool CW>
 __device__ __forceinline__ TetRec walk_rec(const VolArgs &A, int k, bool whole = false) {
   if constexpr (CW) {
@@ -388,30 +361,10 @@ __device__ __forceinline__ TetRec walk_rec(const VolArgs &A, int k, bool whole =
   }
 }
 
-// exp 13: the start tet and its compact record from the hint cell itself
-// (k_hint_inline), one read of neighbouring cells instead of cell -> record
-__device__ __forceinline__ int hint_with_rec(const VolArgs &A, D3 p, TetRec &t) {
-  const int cx = wclamp((p.x - A.g.lo[0]) * A.g.inv[0], A.g.dim[0]);
-  const int cy = wclamp((p.y - A.g.lo[1]) * A.g.inv[1], A.g.dim[1]);
-  const int cz = wclamp((p.z - A.g.lo[2]) * A.g.inv[2], A.g.dim[2]);
-  const int64_t c = gcell(A.g, cx, cy, cz);
-  const uint4 a = A.hrec[2 * c], b = A.hrec[2 * c + 1];
-  int k = (int)a.x;
-  if (k) {
-    WRec r;
-    r.w[0] = a.y; r.w[1] = a.z; r.w[2] = a.w; r.w[3] = b.x; r.w[4] = b.y; r.w[5] = b.z;
-    t = wrec_decode(r, A.tets, k);
-    return k;
-  }
-  k = hint_search(A.grid, A.g.dim[0], A.g.dim[1], A.g.dim[2], cx, cy, cz);
-  t = wrec_load(A.wrec, A.tets, k);
-  return k;
-}
-
 // FAR: the compact records have far neighbour fields (VolArgs.far); without
 // them the walk compiles no resolution path
 // PM: as in k_walk
-template <int LAYOUT, int S, bool TIES, bool CW, bool HREC = false, bool FAR = true, bool PM = false>
+template <int LAYOUT, int S, bool TIES, bool CW, bool FAR = true, bool PM = false>
 __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
   const int64_t b = walk_xcd_remap(blockIdx.x, gridDim.x);
   const int64_t j = b * blockDim.x + threadIdx.x;
@@ -429,8 +382,6 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
     if constexpr (PM) {
       cur = A.grid[j];
       t = walk_rec<CW>(A, cur, FAR && A.exp == 17);
-    } else if constexpr (HREC) {
-      cur = hint_with_rec(A, p, t);
     } else {
       cur = walk_hint(A.grid, A.g, p);
       t = walk_rec<CW>(A, cur, FAR && A.exp == 17);
@@ -442,10 +393,7 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
     int step = 0;
     bool found = false;
     double lam[4];
-    // measurement switch (PMX_EXPERIMENTS=1 only): hint + its record, no walk
-    const bool hint_only = A.exp == 5;
-    if (hint_only) A.elem[i] = t.v[0] + t.nb[0];
-    else if (t.v[0] <= 0) step = 1;                   // !MG_EOK start: let the scan decide
+    if (t.v[0] <= 0) step = 1;                  // !MG_EOK start: let the scan decide
     else {
       D3 C[4] = {ld3(A.xyz, t.v[0]), ld3(A.xyz, t.v[1]), ld3(A.xyz, t.v[2]), ld3(A.xyz, t.v[3])};
       int I[4] = {t.v[0], t.v[1], t.v[2], t.v[3]};
@@ -564,55 +512,42 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
         }
       }
     }
-    if (!hint_only) walk_finish<LAYOUT, S, TIES>(A, i, p, found, step, cur, t, lam, s_cnt, s_sum, s_max, s_min);
+    walk_finish<LAYOUT, S, TIES>(A, i, p, found, step, cur, t, lam, s_cnt, s_sum, s_max, s_min);
   }
   wave_stats_w(A.wstats + (b * blockDim.x + threadIdx.x) / 64, s_cnt, s_sum, s_max, s_min);
 }
 
+// exp 6: walk on the 32-B records although the compact ones are there
 template <int LAYOUT, int S>
 static void launch_walk_t(const VolArgs &a, int64_t nb, hipStream_t s, bool pointmap) {
+  const dim3 g((unsigned)nb), bl(256);
+  const bool cw = a.wrec && a.exp != 6;
   if (pointmap) {
-    // point-map starts: the same variants, without the measurement switches
-    // of the launch shape; the compact records' far fields always resolvable
+    // point-map starts: the compact records' far fields always resolvable
     if (a.ref_walk) {
-      if (a.inline_ties) hipLaunchKernelGGL((k_walk<LAYOUT, S, true, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((k_walk<LAYOUT, S, false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    } else if (a.wrec && a.exp != 6) {
-      if (a.inline_ties)
-        hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, false, true, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, false, true, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+      if (a.inline_ties) hipLaunchKernelGGL((k_walk<LAYOUT, S, true, true>), g, bl, 0, s, a);
+      else hipLaunchKernelGGL((k_walk<LAYOUT, S, false, true>), g, bl, 0, s, a);
+    } else if (cw) {
+      if (a.inline_ties) hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, true, true>), g, bl, 0, s, a);
+      else hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, true, true>), g, bl, 0, s, a);
     } else {
-      if (a.inline_ties)
-        hipLaunchKernelGGL((k_walks<LAYOUT, S, true, false, false, false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_walks<LAYOUT, S, false, false, false, false, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
+      if (a.inline_ties) hipLaunchKernelGGL((k_walks<LAYOUT, S, true, false, false, true>), g, bl, 0, s, a);
+      else hipLaunchKernelGGL((k_walks<LAYOUT, S, false, false, false, true>), g, bl, 0, s, a);
     }
     return;
   }
   if (a.ref_walk) {
-    if (a.inline_ties) hipLaunchKernelGGL((k_walk<LAYOUT, S, true>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_walk<LAYOUT, S, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
-  } else if (a.wrec && a.exp != 6) {           // exp 6: walk on the 32-B records (A/B)
-    // exp 11 / 12: 128- / 64-thread workgroups (A/B of the dispatch granularity)
-    const unsigned bs = a.exp == 11 ? 128u : a.exp == 12 ? 64u : 256u;
-    const unsigned nbb = (unsigned)((a.nlist + bs - 1) / bs);
-    if (a.exp == 13 && a.hrec && a.inline_ties)
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, true>), dim3(nbb), dim3(bs), 0, s, a);
-    else if (a.inline_ties && a.far)
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, false, true>), dim3(nbb), dim3(bs), 0, s, a);
-    else if (a.inline_ties)
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, false, false>), dim3(nbb), dim3(bs), 0, s, a);
-    else if (a.far)
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, false, true>), dim3(nbb), dim3(bs), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, false, false>), dim3(nbb), dim3(bs), 0, s, a);
+    if (a.inline_ties) hipLaunchKernelGGL((k_walk<LAYOUT, S, true>), g, bl, 0, s, a);
+    else hipLaunchKernelGGL((k_walk<LAYOUT, S, false>), g, bl, 0, s, a);
+  } else if (cw) {
+    if (a.inline_ties && a.far) hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, true>), g, bl, 0, s, a);
+    else if (a.inline_ties) hipLaunchKernelGGL((k_walks<LAYOUT, S, true, true, false>), g, bl, 0, s, a);
+    else if (a.far) hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, true>), g, bl, 0, s, a);
+    else hipLaunchKernelGGL((k_walks<LAYOUT, S, false, true, false>), g, bl, 0, s, a);
   } else {
     // (the 32-B records have no far fields)
-    if (a.inline_ties)
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, true, false, false, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL((k_walks<LAYOUT, S, false, false, false, false>), dim3((unsigned)nb), dim3(256), 0, s, a);
+    if (a.inline_ties) hipLaunchKernelGGL((k_walks<LAYOUT, S, true, false, false>), g, bl, 0, s, a);
+    else hipLaunchKernelGGL((k_walks<LAYOUT, S, false, false, false>), g, bl, 0, s, a);
   }
 }
 

@@ -306,12 +306,12 @@ print(json.dumps(out))
 '''
 
 
-def test_lengths_wave_buckets(wave):
-    """The edge-bucket variant of PMMG_prilen (PMX_PRILEN_BUCKETS=1, read when
-    the library loads: a child process)."""
+def test_lengths_wave_wide_index(wave):
+    """The 64-bit-index instantiations of k_prilen (PMX_PRILEN_WIDE=1, read
+    once per process: a child process)."""
     m, met, iso = wave
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PMX_PRILEN_BUCKETS="1")
+    env = dict(os.environ, PMX_PRILEN_WIDE="1")
     p = subprocess.run([sys.executable, "-c", _PB_SCRIPT, root], env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     got = json.loads(p.stdout.strip().splitlines()[-1])

@@ -221,9 +221,14 @@ def test_copy_required_points(transfer):
             assert met[perm[ip], 0] == sols[0][ip, 0]
 
 
-@pytest.mark.parametrize("metric", ["iso", "ani"])
-def test_quality_and_length_stats(transfer, metric):
-    m, x, t, sols = cube_case(7, metric=metric, fields=False)
+@pytest.mark.parametrize("n,metric", [(7, "iso"), (7, "ani"), (9, "graded"), (8, "ani")],
+                         ids=["iso", "ani", "graded-9", "ani-8"])
+def test_quality_and_length_stats(transfer, n, metric):
+    if metric == "graded":
+        m = M.kuhn_cube(n)
+        sols = [M.on_vertices(m, M.graded_iso_metric(n))]
+    else:
+        m, x, t, sols = cube_case(n, metric=metric, fields=False)
     transfer.upload_background(m, sols, 0)
     q = transfer.tetra_qual(m.ne)
     qo = O.tetra_qual(m, sols[0] if metric == "ani" else None)

@@ -103,8 +103,8 @@ def test_count_nodes_matches_oracle(transfer):
         m, idx_ip, idx_comm, np.zeros(nitem, np.int32))
 
 
-@pytest.mark.parametrize("once", [0, 1])
-def test_distributed_prilen_partitions(transfer, once):
+@pytest.mark.parametrize("once,metric", [(0, "shock"), (1, "shock"), (1, "graded")], ids=["0", "1", "1-graded"])
+def test_distributed_prilen_partitions(transfer, once, metric):
     """Both partitions of a split cube: each rank's partial matches the
     oracle's PMMG_computePrilen, and the two partials add up to the whole
     cube's edges (plus the interface edges again in the reference's semantics)."""
@@ -112,7 +112,7 @@ def test_distributed_prilen_partitions(transfer, once):
     parts, nshared = split_partitions(full)
     tot = 0
     for rank, (mr, glob, par) in enumerate(parts):
-        met = M.on_vertices(mr, M.shock_metric)
+        met = M.on_vertices(mr, M.shock_metric if metric == "shock" else M.graded_iso_metric(6))
         p = dict(par, myrank=rank, owner=np.zeros(len(par["a"]), np.int32), exact_once=once)
         transfer.upload_background(mr, [met], 0)
         L = transfer.prilen(par=p)
@@ -405,10 +405,10 @@ print(json.dumps(out))
 '''
 
 
-def test_prilen_edge_buckets_equal_oracle():
-    """The edge-bucket variant of PMMG_prilen (PMX_PRILEN_BUCKETS=1: unique
-    edges by the buckets of their smaller endpoint instead of shell walks --
-    the r04 verdict's alternative, measured in DESIGN.md section 7 r05) gives
+def test_prilen_wide_index_equal_oracle():
+    """The 64-bit-index instantiations of k_prilen (L = false: what the
+    library selects once 6 ne + 5 no longer fits 32 bits; PMX_PRILEN_WIDE=1,
+    read once per process, selects them at any size: a child process) give
     the oracle's statistics: iso graded and tensor metrics, and the two
     partitions of a distributed mesh (parallel edges excluded, exactly once)."""
     import json
@@ -416,7 +416,7 @@ def test_prilen_edge_buckets_equal_oracle():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PMX_PRILEN_BUCKETS="1")
+    env = dict(os.environ, PMX_PRILEN_WIDE="1")
     r = subprocess.run([sys.executable, "-c", _PB_SCRIPT, root], env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]

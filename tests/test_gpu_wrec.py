@@ -164,6 +164,31 @@ def test_hint_sample_order(transfer, monkeypatch):
     assert np.array_equal(out[2][4], out[3][4])                     # the FRESH rebuild: same sample
 
 
+RETIRED = (4, 5, *range(9, 17), *range(19, 27))     # measured and removed
+
+
+def test_retired_experiments_refused(transfer):
+    """A retired run-flag experiment is refused by name before the step
+    enqueues anything (no results become available), and leaves the context
+    as it was: the default step afterwards gives the bytes of the 32-B walk."""
+    m, x, t, sols = cube_case(4)
+    x, t = x[:48].copy(), t[:48].copy()
+    transfer.upload_background(m, sols, 0)
+    transfer.upload_points(x, t)
+    transfer.run(flags=FULL_RECORDS)
+    r = transfer.download()
+    full = (r.elem.copy(), r.status.copy(), [s.copy() for s in r.sols])
+    for v in RETIRED:
+        with pytest.raises(RuntimeError, match="unknown experiment switch"):
+            transfer.run(flags=v << 16)
+        with pytest.raises(RuntimeError, match="no step has run"):
+            transfer.download()
+    transfer.run()
+    r = transfer.download()
+    _assert_same((r.elem, r.status, r.sols), full)
+    assert np.count_nonzero(full[1]) == len(x)
+
+
 COMPACT_FORCED = 18 << 16         # exp 18: compact records whatever their far fields
 
 
