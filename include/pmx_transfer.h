@@ -18,6 +18,10 @@
  *                                             pmx_prilen
  *   PMMG_graph_meshElts2metis / PMMG_computeWgt (src/metis_pmmg.c:746-823,
  *       280-301)                           -> pmx_metis_graph / pmx_face_weights
+ *   PMMG_check_grps_contiguity / PMMG_check_part_contiguity
+ *       (src/metis_pmmg.c:446-529, 312-392) -> pmx_contiguity
+ *   PMMG_fix_contiguity_split / _centralized / PMMG_fix_contiguity
+ *       (src/moveinterfaces_pmmg.c:377-611) -> pmx_fix_contiguity
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -317,7 +321,10 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * batches (always recorded; -1 before the first call).
  * which = 8: the device time of the last pmx_metis_graph, summed over its
  * kernels; 9 / 10 / 11 its count, scan and fill alone (-1 before the first
- * call). */
+ * call).
+ * which = 12 / 13: the labelling kernels / the replay and recolour kernels of
+ * the last pmx_contiguity or pmx_fix_contiguity, summed (-1 before the first
+ * call or after a refusal). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -607,6 +614,50 @@ int pmx_metis_graph(pmx_ctx *ctx, int metRidTyp, int32_t *xadj, int32_t *adjncy,
  * a face[i] is outside 12 .. 12*ne+11 or belongs to a deleted tet, and for
  * pmx_metis_graph's refusals. */
 int pmx_face_weights(pmx_ctx *ctx, int metRidTyp, int64_t n, const int *face, double *wgt);
+
+/* Partition contiguity of the uploaded (or promoted) group, on the tet
+ * adjacency pmx_metis_graph reads.  Both calls refuse (return 0,
+ * pmx_last_error): no group uploaded, 4*ne >= 2^31, a deleted tet (v[0] <= 0:
+ * these callers run on packed meshes).  Host arrays are written only on
+ * success.
+ *
+ * pmx_contiguity: the face-connected components of the graph restricted to
+ * equal part values -- PMMG_check_part_contiguity (src/metis_pmmg.c:312-392)
+ * for every part at once, and with part == NULL (one colour)
+ * PMMG_check_grps_contiguity (:446-529) of the group.  part: ne entries, tet k
+ * at k-1.  counts[p] (nparts entries, may be NULL): the components of part p
+ * (the reference returns the last part's); values outside 0..nparts-1 are
+ * labelled but counted nowhere.  label[k-1] (ne entries, may be NULL): the
+ * smallest 1-based tet of k's component, the head the reference's ascending
+ * scans find.  *ncomp: all components. */
+int pmx_contiguity(pmx_ctx *ctx, const int32_t *part, int32_t nparts, int32_t *counts, int32_t *label,
+                   int64_t *ncomp);
+
+/* ncomp: components of the partition as given.  nmerged / nmerged_tets: lists
+ * merged into a neighbouring colour and their tets.  ncannot: the reference's
+ * "Cannot merge" warnings (a list with no neighbour outside).  counter: the
+ * reference's counter.  rounds: hooking rounds over all labellings; relabels:
+ * labellings after the first; replays: replay launches; replay_steps: tets
+ * the replays dequeued. */
+typedef struct {
+  int64_t ncomp, nmerged, nmerged_tets, ncannot, counter;
+  int64_t rounds, relabels, replays, replay_steps;
+} pmx_contig_stats;
+
+/* PMMG_fix_contiguity_split / _centralized (src/moveinterfaces_pmmg.c:377-523)
+ * and PMMG_fix_contiguity after interface displacement (:525-611) on part
+ * (in/out, ne entries): for each colour of colors[0..ncolors-1], in that
+ * order, every face-connected piece but the largest is merged into the colour
+ * of the first neighbouring tet its list meets -- the reference's lists, ties
+ * and merge targets exactly.  colors NULL = 0..ncolors-1
+ * (the split / centralized form); the interface-displacement form passes
+ * colors[i] = nprocs*i + myrank, other values in part are merge targets only.
+ * Duplicate colours and a NULL part are refused.  replay_steps: dequeues per
+ * component per replay launch, 0 = the default (1024).  st may be NULL.
+ * pmx_kernel_ms(ctx, 12 / 13): labelling / replay and recolour device time of
+ * the last of these two calls. */
+int pmx_fix_contiguity(pmx_ctx *ctx, int32_t *part, int32_t ncolors, const int32_t *colors,
+                       int64_t replay_steps, pmx_contig_stats *st);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

@@ -140,6 +140,12 @@ class SurfaceView(C.Structure):
     ]
 
 
+class ContigStats(C.Structure):
+    """pmx_contig_stats."""
+    _fields_ = [(n, i64) for n in ("ncomp", "nmerged", "nmerged_tets", "ncannot", "counter", "rounds", "relabels",
+                                   "replays", "replay_steps")]
+
+
 INQUA, OUTQUA, LESQUA = 0, 1, 2
 
 
@@ -199,6 +205,8 @@ SIGNATURES = {
     "pmx_prilen": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ParEdges), C.POINTER(LenStats)]),
     "pmx_metis_graph": (C.c_int, [C.c_void_p, C.c_int, i32ptr, i32ptr, i32ptr, i64, C.POINTER(i64)]),
     "pmx_face_weights": (C.c_int, [C.c_void_p, C.c_int, i64, iptr, dptr]),
+    "pmx_contiguity": (C.c_int, [C.c_void_p, i32ptr, C.c_int32, i32ptr, i32ptr, C.POINTER(i64)]),
+    "pmx_fix_contiguity": (C.c_int, [C.c_void_p, i32ptr, C.c_int32, i32ptr, i64, C.POINTER(ContigStats)]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

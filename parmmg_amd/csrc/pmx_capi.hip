@@ -455,6 +455,8 @@ void pmx_destroy(pmx_ctx *ctx) {
   for (auto &e : ctx->events) hipEventDestroy(e);
   for (auto &e : ctx->more_ev) hipEventDestroy(e);
   for (auto &e : ctx->graph_ev) hipEventDestroy(e);
+  for (auto &e : ctx->contig_ev)
+    if (e) hipEventDestroy(e);
   if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_fork2) hipEventDestroy(ctx->ev_fork2);
   if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
@@ -1736,6 +1738,7 @@ int pmx_timing_reset(pmx_ctx *ctx) {
 double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && which == 7) return pmx_more_kernel_ms(ctx);
   if (ctx && which >= 8 && which <= 11) return pmx_graph_kernel_ms(ctx, which);
+  if (ctx && (which == 12 || which == 13)) return pmx_contig_kernel_ms(ctx, which);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
@@ -2095,6 +2098,8 @@ void pmx_ctx::free_all() {
   dfree(d_etag); dfree(d_pn); dfree(d_xpn); dfree(d_pxp); dfree(d_pedge_tag);
   dfree(d_gdeg); dfree(d_gxadj); dfree(d_gadj); dfree(d_gwgt); dfree(d_gface); dfree(d_gflag); dfree(d_gtmp); dfree(d_gfw);
   graph_ev_n = 0;
+  dfree(d_cpar); dfree(d_cmark); dfree(d_cstamp); dfree(d_cqueue); dfree(d_ctab); dfree(d_crec); dfree(d_crecol); dfree(d_cctl);
+  contig_label_ms = contig_replay_ms = -1.0;
   have_ntet = false;
   stat_np = -1;
 }

@@ -185,6 +185,18 @@ struct pmx_ctx {
   DevBuf<double> d_gfw;
   std::vector<hipEvent_t> graph_ev;
   int graph_ev_n = 0;
+  // Partition contiguity (pmx_contiguity / pmx_fix_contiguity, pmx_contig.hip),
+  // ne + 1 words each: parents (labels once converged), marks, the replay's
+  // visit stamps, its queues (the labelling's per-root sizes before that);
+  // the component table, the replay records, the recolour list, the control
+  // words {changed, bad record, deleted tet, roots, unfinished replays, replay
+  // error}; the event pair and the summed times of the last call (-1: none)
+  DevBuf<int> d_cpar, d_cmark, d_cstamp, d_cqueue;
+  DevBuf<int4> d_ctab, d_crec;
+  DevBuf<int2> d_crecol;
+  DevBuf<unsigned> d_cctl;
+  hipEvent_t contig_ev[2] = {};
+  double contig_label_ms = -1.0, contig_replay_ms = -1.0;
   int64_t stat_np = -1;                 // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
@@ -328,5 +340,8 @@ double pmx_more_kernel_ms(pmx_ctx *ctx);
 // pmx_kernel_ms(ctx, 8..11): the last pmx_metis_graph -- its kernels summed,
 // the count, the scan, the fill (pmx_stats.hip)
 double pmx_graph_kernel_ms(pmx_ctx *ctx, int which);
+// pmx_kernel_ms(ctx, 12 / 13): the labelling / the replay and recolour kernels
+// of the last pmx_contiguity or pmx_fix_contiguity, summed (pmx_contig.hip)
+double pmx_contig_kernel_ms(pmx_ctx *ctx, int which);
 // error of a call made without a context (pmx_last_error(NULL), per thread)
 void pmx_set_noctx_error(const char *msg);

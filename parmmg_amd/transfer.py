@@ -12,6 +12,9 @@ Names and argument meaning follow the reference:
   ``PMMG_prilen`` (src/quality_pmmg.c).
 * :meth:`Transfer.metis_graph`, :meth:`Transfer.face_weights` --
   ``PMMG_graph_meshElts2metis`` / ``PMMG_computeWgt`` (src/metis_pmmg.c).
+* :meth:`Transfer.contiguity`, :meth:`Transfer.fix_contiguity` --
+  ``PMMG_check_grps_contiguity`` / ``PMMG_check_part_contiguity``
+  (src/metis_pmmg.c) and ``PMMG_fix_contiguity*`` (src/moveinterfaces_pmmg.c).
 
 Errors follow the reference's 1/0 convention at the C ABI and surface here as
 ``RuntimeError`` with ``pmx_last_error``.  Everything runs on the GPU; there is
@@ -554,6 +557,43 @@ class Transfer:
         w = np.zeros(len(f))
         self._chk(self.lib.pmx_face_weights(self.ctx, met_rid_typ, len(f), _ip(f), _dp(w)), "pmx_face_weights")
         return w
+
+    def contiguity(self, part: np.ndarray | None = None, nparts: int = 1):
+        """The face-connected components of the uploaded (or promoted) group
+        restricted to equal part values (pmx_contiguity): (ncomp, counts
+        (nparts,), label (ne,)) with label[k-1] the smallest 1-based tet of tet
+        k's component.  part=None: one colour, PMMG_check_grps_contiguity."""
+        ne = self.bg_ne
+        p = None if part is None else np.ascontiguousarray(part, np.int32)
+        if p is not None and p.shape != (ne,):
+            raise ValueError(f"part has shape {p.shape}, the group has {ne} tets")
+        counts = np.zeros(max(nparts, 0), np.int32)
+        label = np.zeros(ne, np.int32)
+        n = C.c_int64(0)
+        i32 = lambda a: a.ctypes.data_as(N.i32ptr) if a is not None and a.size else None
+        self._chk(self.lib.pmx_contiguity(self.ctx, i32(p), nparts, i32(counts), i32(label), C.byref(n)),
+                  "pmx_contiguity")
+        return n.value, counts, label
+
+    def fix_contiguity(self, part: np.ndarray, colors_or_n, replay_steps: int = 0):
+        """PMMG_fix_contiguity_split / _centralized / PMMG_fix_contiguity on a
+        copy of part (pmx_fix_contiguity): (part, stats).  colors_or_n: the
+        number of colours (0..n-1, in that order) or the list of colours to
+        process in order; stats: the fields of pmx_contig_stats as a dict."""
+        ne = self.bg_ne
+        p = np.array(part, np.int32, order="C")
+        if p.shape != (ne,):
+            raise ValueError(f"part has shape {p.shape}, the group has {ne} tets")
+        if np.ndim(colors_or_n) == 0:
+            ncol, col = int(colors_or_n), None
+        else:
+            col = np.ascontiguousarray(colors_or_n, np.int32)
+            ncol = len(col)
+        st = N.ContigStats()
+        self._chk(self.lib.pmx_fix_contiguity(self.ctx, p.ctypes.data_as(N.i32ptr), ncol,
+                                              col.ctypes.data_as(N.i32ptr) if col is not None else None,
+                                              replay_steps, C.byref(st)), "pmx_fix_contiguity")
+        return p, {f: getattr(st, f) for f, _ in st._fields_}
 
     def upload_new_tets(self, tets: np.ndarray):
         """The new mesh's tets, (ne+1, 4) with 0-based point indices (v[0] < 0:
