@@ -22,6 +22,8 @@
  *       (src/metis_pmmg.c:446-529, 312-392) -> pmx_contiguity
  *   PMMG_fix_contiguity_split / _centralized / PMMG_fix_contiguity
  *       (src/moveinterfaces_pmmg.c:377-611) -> pmx_fix_contiguity
+ *   PMMG_split_eachGrp (src/grpsplit_pmmg.c:1267-1445)
+ *                                          -> pmx_split_groups / pmx_split_fetch
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -324,7 +326,9 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * call).
  * which = 12 / 13: the labelling kernels / the replay and recolour kernels of
  * the last pmx_contiguity or pmx_fix_contiguity, summed (-1 before the first
- * call or after a refusal). */
+ * call or after a refusal).
+ * which = 14 / 15: the last pmx_split_groups / the last pmx_split_fetch after
+ * it (-1 before the first, after a refusal of the plan and after a release). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -658,6 +662,71 @@ typedef struct {
  * the last of these two calls. */
 int pmx_fix_contiguity(pmx_ctx *ctx, int32_t *part, int32_t ncolors, const int32_t *colors,
                        int64_t replay_steps, pmx_contig_stats *st);
+
+/* The uploaded (or promoted) group split by a partition: the new groups of
+ * PMMG_split_eachGrp (src/grpsplit_pmmg.c:1267-1445) -- the tets, points,
+ * adjacency and internal communicators PMMG_splitGrps_countTetPerGrp and
+ * PMMG_splitGrps_fillGroup leave behind, the groups filled in the order
+ * g = 0..ngrp-1 ("Group split").  Not produced: xTetra /
+ * xPoint appends, the MG_PARBDY tags, PMMG_splitGrps_cleanMesh.
+ * The tet records keep adja / 4 only: the neighbour's face is found as the one
+ * that points back, so no two tets may share two faces.
+ *
+ * The old group's internal communicators (all optional: comm NULL, or counts
+ * 0): face2int_face_comm_index1/2 (nface entries), node2int_node_comm_index1/2
+ * (nnode entries), int_face_comm->nitem and int_node_comm->nitem on entry. */
+typedef struct {
+  int64_t nface, nnode;
+  const int *face_index1, *face_index2, *node_index1, *node_index2;
+  int64_t int_face_nitem, int_node_nitem;
+} pmx_split_comm;
+/* tets, points (poiPerGrp), face2int_face_comm and node2int_node_comm entries
+ * of one new group */
+typedef struct { int64_t ne, np, nface, nnode; } pmx_split_sizes;
+
+/* The plan: everything is computed and kept on the device.  part: ne entries,
+ * tet k at k-1, values 0..ngrp-1, every value used.  sizes: ngrp entries.
+ * tet_new (ne ints, may be NULL): the local id of old tet k at k-1, the
+ * reference's meshOld->tetra[k].flag.  *int_face_nitem / *int_node_nitem: the
+ * internal communicators' nitem after the split.  Any ngrp <= ne works (no
+ * table of ne x ngrp entries exists).  Returns 0 (pmx_last_error), the host
+ * arrays untouched: no group uploaded; 4*ne >= 2^31; a deleted tet; part NULL;
+ * ngrp < 1; a part value outside 0..ngrp-1; an empty part; 12*ne_g + 11 >= 2^31
+ * for a group; an input face entry outside 12..12*ne+11 or on a face whose
+ * adjacency is not 0; an input node outside 1..np.
+ * pmx_kernel_ms(ctx, 14): the plan's device time (first to last device
+ * operation of the call: the upload of part and the small table downloads
+ * included, the tet_new download not); 15: the last fetch's (gather kernel
+ * and copies); -1 before the first. */
+int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_split_comm *comm,
+                     pmx_split_sizes *sizes, int *tet_new, int64_t *int_face_nitem, int64_t *int_node_nitem);
+
+/* One new group's arrays, sized by the plan's sizes[g]; every pointer may be
+ * NULL (not fetched):
+ *   tet_old      ne ints: the old tet of local tet j at j-1 (tetra[j].flag)
+ *   tetra_v      4*(ne+1) ints, Mmg layout: rows 1..ne written, local point ids
+ *   adja         4*ne+5 ints, Mmg layout, all written: 4*j'+f' inside the
+ *                group, 0 on the old boundary and on the new interface faces
+ *   point_old    np ints: the old vertex of local point i at i-1
+ *   face_index1/2  nface ints each: 12*j + 3*f + iploc and the position
+ *   node_index1/2  nnode ints each: the local point and its value
+ *   xyz          3*(np+1) doubles, rows 1..np written
+ *   sols         nsol = 0 (none) or the number of uploaded solutions, of the
+ *                uploaded sizes: m holds (np+1)*size doubles, rows 1..np written */
+typedef struct {
+  int *tet_old, *tetra_v, *adja, *point_old, *face_index1, *face_index2, *node_index1, *node_index2;
+  double *xyz;
+  int nsol;
+  const pmx_sol_view *sols;
+} pmx_split_out;
+/* Returns 0, the arrays untouched: no plan (none made, released, or dropped by
+ * a later pmx_upload_background / pmx_promote_background); g outside
+ * 0..ngrp-1; solution views that do not match the uploaded ones.  The slices
+ * are copied straight into the arrays, so a device error during the copies
+ * (the only failure left after these checks) may leave them partly written. */
+int pmx_split_fetch(pmx_ctx *ctx, int32_t g, const pmx_split_out *out);
+/* Frees the plan's device memory (pmx_destroy does too). */
+int pmx_split_release(pmx_ctx *ctx);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

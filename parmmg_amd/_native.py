@@ -146,6 +146,25 @@ class ContigStats(C.Structure):
                                    "replays", "replay_steps")]
 
 
+class SplitComm(C.Structure):
+    """pmx_split_comm: the old group's internal communicators."""
+    _fields_ = [("nface", i64), ("nnode", i64),
+                ("face_index1", iptr), ("face_index2", iptr), ("node_index1", iptr), ("node_index2", iptr),
+                ("int_face_nitem", i64), ("int_node_nitem", i64)]
+
+
+class SplitSizes(C.Structure):
+    """pmx_split_sizes."""
+    _fields_ = [(n, i64) for n in ("ne", "np", "nface", "nnode")]
+
+
+class SplitOut(C.Structure):
+    """pmx_split_out: one new group's arrays (NULL: not fetched)."""
+    _fields_ = [(n, iptr) for n in ("tet_old", "tetra_v", "adja", "point_old", "face_index1", "face_index2",
+                                    "node_index1", "node_index2")] + \
+               [("xyz", dptr), ("nsol", C.c_int), ("sols", C.POINTER(SolView))]
+
+
 INQUA, OUTQUA, LESQUA = 0, 1, 2
 
 
@@ -207,6 +226,10 @@ SIGNATURES = {
     "pmx_face_weights": (C.c_int, [C.c_void_p, C.c_int, i64, iptr, dptr]),
     "pmx_contiguity": (C.c_int, [C.c_void_p, i32ptr, C.c_int32, i32ptr, i32ptr, C.POINTER(i64)]),
     "pmx_fix_contiguity": (C.c_int, [C.c_void_p, i32ptr, C.c_int32, i32ptr, i64, C.POINTER(ContigStats)]),
+    "pmx_split_groups": (C.c_int, [C.c_void_p, i32ptr, C.c_int32, C.POINTER(SplitComm), C.POINTER(SplitSizes), iptr,
+                                   C.POINTER(i64), C.POINTER(i64)]),
+    "pmx_split_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SplitOut)]),
+    "pmx_split_release": (C.c_int, [C.c_void_p]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

@@ -544,6 +544,7 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
   // with the device buffers)
   ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
   ctx->have_pmap = false;
+  ctx->split_valid = false;
   ctx->eager_nch = 0;
   ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = false;
   ctx->stat_np = -1;
@@ -1739,6 +1740,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && which == 7) return pmx_more_kernel_ms(ctx);
   if (ctx && which >= 8 && which <= 11) return pmx_graph_kernel_ms(ctx, which);
   if (ctx && (which == 12 || which == 13)) return pmx_contig_kernel_ms(ctx, which);
+  if (ctx && (which == 14 || which == 15)) return pmx_split_kernel_ms(ctx, which);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
@@ -1964,6 +1966,7 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   // the background invalid until this completes
   ctx->have_bg = ctx->have_derived = ctx->have_tetv = ctx->have_qual = ctx->have_ptag = ctx->have_csr = ctx->have_surf = false;
   ctx->have_pmap = false;
+  ctx->split_valid = false;
   ctx->bg_btv = false;                     // records from the new tets (or the caller's adja), not d_btv
   ctx->stat_np = -1;
   const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
@@ -2100,6 +2103,7 @@ void pmx_ctx::free_all() {
   graph_ev_n = 0;
   dfree(d_cpar); dfree(d_cmark); dfree(d_cstamp); dfree(d_cqueue); dfree(d_ctab); dfree(d_crec); dfree(d_crecol); dfree(d_cctl);
   contig_label_ms = contig_replay_ms = -1.0;
+  pmx_split_free(this);
   have_ntet = false;
   stat_np = -1;
 }

@@ -197,6 +197,12 @@ struct pmx_ctx {
   DevBuf<unsigned> d_cctl;
   hipEvent_t contig_ev[2] = {};
   double contig_label_ms = -1.0, contig_replay_ms = -1.0;
+  // Group split (pmx_split_groups / pmx_split_fetch, pmx_split.hip): the plan
+  // with its device buffers, valid until the next
+  // background upload or promotion; device times of the last plan / fetch
+  struct pmx_split_plan *split = nullptr;
+  bool split_valid = false;
+  double split_plan_ms = -1.0, split_fetch_ms = -1.0;
   int64_t stat_np = -1;                 // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
@@ -343,5 +349,9 @@ double pmx_graph_kernel_ms(pmx_ctx *ctx, int which);
 // pmx_kernel_ms(ctx, 12 / 13): the labelling / the replay and recolour kernels
 // of the last pmx_contiguity or pmx_fix_contiguity, summed (pmx_contig.hip)
 double pmx_contig_kernel_ms(pmx_ctx *ctx, int which);
+// pmx_kernel_ms(ctx, 14 / 15): the last split plan / the last fetch; the plan
+// and its buffers freed (pmx_split.hip)
+double pmx_split_kernel_ms(pmx_ctx *ctx, int which);
+void pmx_split_free(pmx_ctx *ctx);
 // error of a call made without a context (pmx_last_error(NULL), per thread)
 void pmx_set_noctx_error(const char *msg);

@@ -15,6 +15,9 @@ Names and argument meaning follow the reference:
 * :meth:`Transfer.contiguity`, :meth:`Transfer.fix_contiguity` --
   ``PMMG_check_grps_contiguity`` / ``PMMG_check_part_contiguity``
   (src/metis_pmmg.c) and ``PMMG_fix_contiguity*`` (src/moveinterfaces_pmmg.c).
+* :meth:`Transfer.split_groups`, :meth:`Transfer.split_fetch`,
+  :meth:`Transfer.split_release` -- the new groups of ``PMMG_split_eachGrp``
+  (src/grpsplit_pmmg.c).
 
 Errors follow the reference's 1/0 convention at the C ABI and surface here as
 ``RuntimeError`` with ``pmx_last_error``.  Everything runs on the GPU; there is
@@ -594,6 +597,79 @@ class Transfer:
                                               col.ctypes.data_as(N.i32ptr) if col is not None else None,
                                               replay_steps, C.byref(st)), "pmx_fix_contiguity")
         return p, {f: getattr(st, f) for f, _ in st._fields_}
+
+    def split_groups(self, part: np.ndarray, ngrp: int, comm: dict | None = None) -> dict:
+        """PMMG_split_eachGrp of the uploaded (or promoted) group by part
+        (pmx_split_groups): the plan stays on the device, split_fetch returns
+        one group.  comm: the old group's internal communicators, any of
+        face_index1/2, node_index1/2, int_face_nitem, int_node_nitem.  Returns
+        sizes ((ngrp, 4) int64: ne, np, nface, nnode per group), tet_new (ne,)
+        and the two final nitem."""
+        ne = self.bg_ne
+        p = np.ascontiguousarray(part, np.int32)
+        if p.shape != (ne,):
+            raise ValueError(f"part has shape {p.shape}, the group has {ne} tets")
+        comm = comm or {}
+        arr = {k: np.ascontiguousarray(comm.get(k, np.zeros(0)), np.int32)
+               for k in ("face_index1", "face_index2", "node_index1", "node_index2")}
+        if len(arr["face_index1"]) != len(arr["face_index2"]) or len(arr["node_index1"]) != len(arr["node_index2"]):
+            raise ValueError("index1 and index2 of a communicator differ in length")
+        c = N.SplitComm()
+        c.nface, c.nnode = len(arr["face_index1"]), len(arr["node_index1"])
+        for k, a in arr.items():
+            setattr(c, k, _ip(a) if a.size else None)
+        c.int_face_nitem = int(comm.get("int_face_nitem", 0))
+        c.int_node_nitem = int(comm.get("int_node_nitem", 0))
+        sizes = (N.SplitSizes * max(ngrp, 1))()
+        tet_new = np.zeros(ne, np.int32)
+        fn, nn = C.c_int64(0), C.c_int64(0)
+        self._split_sizes = None
+        self._chk(self.lib.pmx_split_groups(self.ctx, p.ctypes.data_as(N.i32ptr), ngrp, C.byref(c), sizes,
+                                            _ip(tet_new) if ne else None, C.byref(fn), C.byref(nn)),
+                  "pmx_split_groups")
+        sz = np.array([[s.ne, s.np, s.nface, s.nnode] for s in sizes[:ngrp]], np.int64).reshape(ngrp, 4)
+        self._split_sizes = sz
+        return {"sizes": sz, "tet_new": tet_new, "int_face_nitem": fn.value, "int_node_nitem": nn.value}
+
+    def split_fetch(self, g: int, data: bool = True) -> dict:
+        """One new group of the last split_groups (pmx_split_fetch): tet_old
+        (ne,), tetra_v ((ne+1, 4), row 0 unused), adja (4*ne+5, Mmg layout),
+        point_old (np,), face_index1/2, node_index1/2; with data also xyz
+        ((np+1, 3), row 0 unused, as Mesh wants it) and sols, the rows of every
+        uploaded solution ((np+1, size) each)."""
+        sz = getattr(self, "_split_sizes", None)
+        if sz is None or not 0 <= g < len(sz):
+            neg = npg = nf = nn = 0       # the library refuses: no plan, or g out of range
+        else:
+            neg, npg, nf, nn = (int(v) for v in sz[g])
+        # the library writes every entry but row 0 of the 1-based arrays
+        d = {"tet_old": np.empty(neg, np.int32), "tetra_v": np.empty((neg + 1, 4), np.int32),
+             "adja": np.empty(4 * neg + 5, np.int32), "point_old": np.empty(npg, np.int32),
+             "face_index1": np.empty(nf, np.int32), "face_index2": np.empty(nf, np.int32),
+             "node_index1": np.empty(nn, np.int32), "node_index2": np.empty(nn, np.int32)}
+        d["tetra_v"][0] = 0
+        o = N.SplitOut()
+        for k, a in d.items():
+            setattr(o, k, _ip(a))
+        if data:
+            d["xyz"] = np.empty((npg + 1, 3))
+            d["sols"] = [np.empty((npg + 1, s)) for s in self.sizes]
+            for a in [d["xyz"]] + d["sols"]:
+                a[0] = 0.0
+            o.xyz = _dp(d["xyz"])
+            views = (N.SolView * max(len(self.sizes), 1))()
+            for i, a in enumerate(d["sols"]):
+                views[i].size = self.sizes[i]
+                views[i].m = _dp(a)
+            o.nsol = len(self.sizes)
+            o.sols = views
+        self._chk(self.lib.pmx_split_fetch(self.ctx, g, C.byref(o)), "pmx_split_fetch")
+        return d
+
+    def split_release(self):
+        """Free the plan's device memory (pmx_split_release)."""
+        self._split_sizes = None
+        self._chk(self.lib.pmx_split_release(self.ctx), "pmx_split_release")
 
     def upload_new_tets(self, tets: np.ndarray):
         """The new mesh's tets, (ne+1, 4) with 0-based point indices (v[0] < 0:
