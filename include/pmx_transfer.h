@@ -289,6 +289,10 @@ int pmx_pointmap_stats(pmx_ctx *ctx, int64_t atomics[2]);
 /* Inspection: copy the volume hint grid of the last run to host (cap cells);
  * returns the number of cells (0 on error). */
 int64_t pmx_debug_hint_grid(pmx_ctx *ctx, int *host, int64_t cap);
+/* Inspection: the process-wide number of live device and pinned allocations
+ * the library owns (memory handed out by pmx_device_alloc is the caller's and
+ * is not counted). */
+int64_t pmx_debug_live_allocations(void);
 
 /* ---- background topology on the device (the old-group
  * snapshot of src/grpsplit_pmmg.c:207-418) ------------------------------- */

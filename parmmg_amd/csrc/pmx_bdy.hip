@@ -973,7 +973,7 @@ bool pmx_ctx::fan_rotation(hipStream_t s, unsigned *d_bad, bool check) {
 // PMX_FAN_ROTATION=0 keeps the sort (A/B, tests).
 bool pmx_ctx::check_fans(hipStream_t s) {
   fan_rot = false;
-  h_nbad[4] = 1u;
+  h_nbad.p[4] = 1u;
   if (nt < 1 || 3 * (nt + 1) * (int64_t)FAN_CAP > (int64_t)INT32_MAX) return true;   // int windows
   const char *e = getenv("PMX_FAN_ROTATION");
   if (e && e[0] == '0') return true;
@@ -993,7 +993,7 @@ bool pmx_ctx::check_fans(hipStream_t s) {
     return false;
   }
   if (!fan_rotation(s, d_wfar.p + 3, true)) return false;
-  if (hipMemcpyAsync(h_nbad + 4, d_wfar.p + 3, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) {
+  if (hipMemcpyAsync(h_nbad.p + 4, d_wfar.p + 3, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) {
     err = "node trias: check";
     return false;
   }
@@ -1092,13 +1092,7 @@ bool pmx_ctx::size_tria_grid() {
     cells *= d;
   }
   tcells = nt > 0 ? cells : 0;
-  if (tcells && d_tgrid_cap < (size_t)cells) {
-    if (d_tgrid) hipFree(d_tgrid);
-    d_tgrid = nullptr;
-    d_tgrid_cap = 0;
-    if (hipMalloc((void **)&d_tgrid, sizeof(int) * (size_t)cells) != hipSuccess) { err = "hipMalloc tgrid"; return false; }
-    d_tgrid_cap = (size_t)cells;
-  }
+  if (tcells && !pmx_dgrow(this, d_tgrid, (size_t)cells)) { err = "hipMalloc tgrid"; return false; }
   return true;
 }
 
@@ -1107,7 +1101,7 @@ static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap = false) {
   BdyArgs B{};
   B.xyz = c->d_xyz.p; B.tris = c->d_tris.p; B.trn = c->d_trn.p; B.ntrange = c->d_ntrange.p; B.ntlist = c->d_ntlist.p;
   B.sol = c->d_sol.p; B.sd = a.sd; B.q = c->d_qxyz.p; B.kind = c->d_kind.p; B.nq = c->nq; B.nt = c->nt;
-  B.hausd = c->hausd; B.grid = c->d_tgrid; B.g = c->tgd;
+  B.hausd = c->hausd; B.grid = c->d_tgrid.p; B.g = c->tgd;
   B.out = c->d_out.p; B.wmask = c->d_wmask.p; B.elem = c->d_elem.p; B.status = c->d_status.p;
   B.steps = c->d_steps.p; B.start = c->d_start.p; B.edge = c->d_edge.p; B.vertex = c->d_vertex.p;
   B.bphi = c->d_bphi.p;
@@ -1138,23 +1132,15 @@ static void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_
 
 bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
   if (nt < 1) { err = "surface points present but the background has no boundary trias"; return false; }
-  if (!d_blist.p || d_blist.cap < (size_t)nq) {
-    if (d_blist.p) hipFree(d_blist.p);
-    if (hipMalloc((void **)&d_blist.p, sizeof(int) * (size_t)std::max<int64_t>(nq, 1)) != hipSuccess) { err = "hipMalloc blist"; return false; }
-    d_blist.cap = (size_t)nq;
-    if (d_olist.p) hipFree(d_olist.p);
-    if (hipMalloc((void **)&d_olist.p, sizeof(int) * (size_t)std::max<int64_t>(nq, 1)) != hipSuccess) { err = "hipMalloc olist"; return false; }
-    d_olist.cap = (size_t)nq;
-  }
+  if (!pmx_dgrow(this, d_blist, (size_t)nq)) { err = "hipMalloc blist"; return false; }
+  if (!pmx_dgrow(this, d_olist, (size_t)nq)) { err = "hipMalloc olist"; return false; }
   if (!pmx_dgrow(this, d_bphi, (size_t)std::max<int64_t>(nq_bdy_ub, 1))) return false;
-  if (!d_ows.p) {
-    if (hipMalloc((void **)&d_ows.p, sizeof(int) * (size_t)OVF_THREADS * 3 * OVF_CAP) != hipSuccess) { err = "hipMalloc ows"; return false; }
-    d_ows.cap = (size_t)OVF_THREADS * 3 * OVF_CAP;
-  }
+  // allocated once (the sequential mode grows it for its own pass)
+  if (!d_ows.p && !pmx_dgrow(this, d_ows, (size_t)OVF_THREADS * 3 * OVF_CAP)) { err = "hipMalloc ows"; return false; }
   // tria hint grid: sized and allocated with the background
   // (pmx_ctx::size_tria_grid), zeroed and built at the head of the surface
   // path (off the main stream); none with point-map starts
-  if (!pointmap && hipMemsetAsync(d_tgrid, 0, sizeof(int) * (size_t)tcells, s) != hipSuccess) {
+  if (!pointmap && hipMemsetAsync(d_tgrid.p, 0, sizeof(int) * (size_t)tcells, s) != hipSuccess) {
     err = "tria hint grid memset";
     return false;
   }
@@ -1162,7 +1148,7 @@ bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
     int64_t nb = (nt + 255) / 256;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_tria_hint_build, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(256), 0, s,
-                       d_tris.p, d_xyz.p, nt, d_tgrid, tgd);
+                       d_tris.p, d_xyz.p, nt, d_tgrid.p, tgd);
   }
   launch_bdy_walks(bdy_args(this, a, pointmap), d_ows.p, s, OVF_THREADS, false, pointmap);
   return hipGetLastError() == hipSuccess;
@@ -1371,12 +1357,7 @@ __global__ __launch_bounds__(64) void k_seq_resolve(BdyArgs A, const int *__rest
 }
 
 bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
-  pmx_ctx *ctx = this;
-  auto ck = [&](hipError_t e, const char *what) {
-    if (e == hipSuccess) return true;
-    ctx->err = std::string("sequential replay: ") + what + ": " + hipGetErrorString(e);
-    return false;
-  };
+  const pmx_call C{this, "sequential replay", s};
   seq_stats[0] = seq_stats[1] = seq_stats[2] = seq_stats[3] = 0;
   if (!surf && !vol) return true;
   if (!have_ntet) {
@@ -1410,17 +1391,17 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
   const unsigned nbt = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_ntet + 255) / 256, 8192));
   const unsigned nbp = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
   // 1. visit order, bases, sequences
-  if (!ck(hipMemsetAsync(key, 0xff, (size_t)n * sizeof(unsigned), s), "memset") ||
-      !ck(hipMemsetAsync(ctl, 0, 64 * sizeof(int), s), "memset"))
+  if (!C.hip(hipMemsetAsync(key, 0xff, (size_t)n * sizeof(unsigned), s), "memset") ||
+      !C.hip(hipMemsetAsync(ctl, 0, 64 * sizeof(int), s), "memset"))
     return false;
   hipLaunchKernelGGL(k_seq_keys, dim3(nbt), dim3(256), 0, s, (const int4 *)d_ntetv.p, n_ntet, key);
   hipLaunchKernelGGL(k_seq_iota, dim3(nbp), dim3(256), 0, s, idx, sstart, sbase, n);
-  if (!ck(hipcub::DeviceRadixSort::SortPairs(d_sqtmp.p, sort_b, (const unsigned *)key, key2, (const int *)idx, idx2,
+  if (!C.hip(hipcub::DeviceRadixSort::SortPairs(d_sqtmp.p, sort_b, (const unsigned *)key, key2, (const int *)idx, idx2,
                                             (int)n, 0, 32, s), "sort"))
     return false;
   hipLaunchKernelGGL(k_seq_flags, dim3(nbp), dim3(256), 0, s, (const unsigned *)key2, (const int *)idx2,
                      (const int8_t *)d_kind.p, n, val);
-  if (!ck(hipcub::DeviceScan::ExclusiveSum(d_sqtmp.p, scan_b, (const unsigned long long *)val, pre, (int)n, s),
+  if (!C.hip(hipcub::DeviceScan::ExclusiveSum(d_sqtmp.p, scan_b, (const unsigned long long *)val, pre, (int)n, s),
           "scan"))
     return false;
   hipLaunchKernelGGL(k_seq_assign, dim3(nbp), dim3(256), 0, s, (const int *)idx2, (const unsigned long long *)val,
@@ -1429,7 +1410,7 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
     // 2. the speculative surface pass
     hipLaunchKernelGGL(k_seq_starts, dim3(nbp), dim3(256), 0, s, (const int *)seq, (const int *)nseq,
                        (const int *)d_elem.p, sstart);
-    if (!ck(hipMemsetAsync(d_counts.p + 1, 0, 2 * sizeof(unsigned), s), "memset")) return false;
+    if (!C.hip(hipMemsetAsync(d_counts.p + 1, 0, 2 * sizeof(unsigned), s), "memset")) return false;
     BdyArgs B = bdy_args(this, a);
     B.seq_start = sstart;
     B.seq_base = sbase;
@@ -1439,20 +1420,20 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
     const int seq_ovf = 2 * OVF_THREADS;
     const size_t ws_ints = (size_t)seq_ovf * GHS_SLOTS * 6;
     if (!pmx_dgrow(this, d_ows, ws_ints) ||
-        !ck(hipMemsetAsync(d_ows.p, 0, ws_ints * sizeof(int), s), "memset"))
+        !C.hip(hipMemsetAsync(d_ows.p, 0, ws_ints * sizeof(int), s), "memset"))
       return false;
     launch_bdy_walks(B, d_ows.p, s, seq_ovf, true);
     // 3. the replay, on the reference's state
-    if (!ck(hipMemsetAsync(d_sqtf.p, 0, (size_t)(nt + 1) * sizeof(int), s), "memset") ||
-        !ck(hipMemsetAsync(d_sqpf.p, 0x80, (size_t)(np + 1) * sizeof(int), s), "memset"))
+    if (!C.hip(hipMemsetAsync(d_sqtf.p, 0, (size_t)(nt + 1) * sizeof(int), s), "memset") ||
+        !C.hip(hipMemsetAsync(d_sqpf.p, 0x80, (size_t)(np + 1) * sizeof(int), s), "memset"))
       return false;
     int hctl[4] = {0, 1, 0, 0};
-    if (!ck(hipMemcpyAsync(ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
+    if (!C.hip(hipMemcpyAsync(ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
     // the replay's candidates, in visit order
     {
       size_t sel_b = 0;
       hipcub::CountingInputIterator<int> it(0);
-      if (!ck(hipcub::DeviceSelect::Flagged(nullptr, sel_b, it, (const uint8_t *)nullptr, (int *)nullptr,
+      if (!C.hip(hipcub::DeviceSelect::Flagged(nullptr, sel_b, it, (const uint8_t *)nullptr, (int *)nullptr,
                                             (int *)nullptr, (int)nq_bdy_ub, s),
               "select") ||
           !pmx_dgrow(this, d_sqflag, (size_t)nq_bdy_ub) || !pmx_dgrow(this, d_sqcand, (size_t)nq_bdy_ub + 1) ||
@@ -1462,7 +1443,7 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
       hipLaunchKernelGGL(k_seq_sflags, dim3(nbs), dim3(256), 0, s, (const int *)seq, (const int *)nseq,
                          (const int *)sstart, (const uint8_t *)d_sqw.p, (const int *)d_elem.p, (int64_t)nq_bdy_ub,
                          d_sqflag.p);
-      if (!ck(hipcub::DeviceSelect::Flagged(d_sqtmp.p, sel_b, it, (const uint8_t *)d_sqflag.p, d_sqcand.p + 1,
+      if (!C.hip(hipcub::DeviceSelect::Flagged(d_sqtmp.p, sel_b, it, (const uint8_t *)d_sqflag.p, d_sqcand.p + 1,
                                             d_sqcand.p, (int)nq_bdy_ub, s),
               "select"))
         return false;
@@ -1474,8 +1455,8 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
       hipLaunchKernelGGL(k_seq_resolve, dim3(1), dim3(64), 0, s, B, (const int *)seq, (const int *)nseq,
                          (const int *)sstart, (const uint8_t *)d_sqw.p, (const int *)sbase, d_sqtf.p, d_sqpf.p, ctl,
                          stk_list, stk_count, nreplay, (const int *)(d_sqcand.p + 1), (const int *)d_sqcand.p);
-      if (!ck(hipMemcpyAsync(hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, s), "ctl") ||
-          !ck(hipStreamSynchronize(s), "sync"))
+      if (!C.hip(hipMemcpyAsync(hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, s), "ctl") ||
+          !C.hip(hipStreamSynchronize(s), "sync"))
         return false;
       if (hctl[2] == 0) break;
       // a replayed query ended stuck: the exhaustive scan of that one point
@@ -1483,7 +1464,7 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
       hctl[0] += 1;
       hctl[1] = -1;
       hctl[2] = 0;
-      if (!ck(hipMemcpyAsync(ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
+      if (!C.hip(hipMemcpyAsync(ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
     }
   }
   if (vol && nq_vol_ub > 0) {
@@ -1494,7 +1475,7 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
     SeqVolArgs SV{vseq, nseq + 1, sstart, sbase, d_sqw.p, d_sqtv.p, ctl + 4, vstk_list, nreplay + 1, nullptr, nullptr};
     // the overflow pass's hash tables: generation 0 = empty (positions start at 1)
     if (!pmx_dgrow(this, d_sqows, seqv_ovf_ws_ints()) ||
-        !ck(hipMemsetAsync(d_sqows.p, 0, seqv_ovf_ws_ints() * sizeof(int), s), "memset"))
+        !C.hip(hipMemsetAsync(d_sqows.p, 0, seqv_ovf_ws_ints() * sizeof(int), s), "memset"))
       return false;
     launch_seqv_spec(a, SV, nq_vol_ub, d_sqows.p, s);
     // the replay's candidates: positions whose speculative start may be wrong,
@@ -1502,27 +1483,27 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
     {
       size_t sel_b = 0;
       hipcub::CountingInputIterator<int> it(0);
-      if (!ck(hipcub::DeviceSelect::Flagged(nullptr, sel_b, it, (const uint8_t *)nullptr, (int *)nullptr,
+      if (!C.hip(hipcub::DeviceSelect::Flagged(nullptr, sel_b, it, (const uint8_t *)nullptr, (int *)nullptr,
                                             (int *)nullptr, (int)nq_vol_ub, s),
               "select") ||
           !pmx_dgrow(this, d_sqflag, (size_t)nq_vol_ub) || !pmx_dgrow(this, d_sqcand, (size_t)nq_vol_ub + 1) ||
           !pmx_dgrow(this, d_sqtmp, sel_b))
         return false;
       launch_seqv_flags(a, SV, nq_vol_ub, d_sqflag.p, s);
-      if (!ck(hipcub::DeviceSelect::Flagged(d_sqtmp.p, sel_b, it, (const uint8_t *)d_sqflag.p, d_sqcand.p + 1,
+      if (!C.hip(hipcub::DeviceSelect::Flagged(d_sqtmp.p, sel_b, it, (const uint8_t *)d_sqflag.p, d_sqcand.p + 1,
                                             d_sqcand.p, (int)nq_vol_ub, s),
               "select"))
         return false;
       SV.ncand = d_sqcand.p;
       SV.cand = d_sqcand.p + 1;
     }
-    if (!ck(hipMemsetAsync(d_sqtv.p, 0, (size_t)(ne + 1) * sizeof(int), s), "memset")) return false;
+    if (!C.hip(hipMemsetAsync(d_sqtv.p, 0, (size_t)(ne + 1) * sizeof(int), s), "memset")) return false;
     int hctl[4] = {0, 1, 0, 0};
-    if (!ck(hipMemcpyAsync(ctl + 4, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
+    if (!C.hip(hipMemcpyAsync(ctl + 4, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
     for (;;) {
       launch_seqv_resolve(a, SV, s);
-      if (!ck(hipMemcpyAsync(hctl, ctl + 4, sizeof hctl, hipMemcpyDeviceToHost, s), "ctl") ||
-          !ck(hipStreamSynchronize(s), "sync"))
+      if (!C.hip(hipMemcpyAsync(hctl, ctl + 4, sizeof hctl, hipMemcpyDeviceToHost, s), "ctl") ||
+          !C.hip(hipStreamSynchronize(s), "sync"))
         return false;
       if (hctl[2] == 0) break;
       // a replayed walk got stuck: k_fallback on that one point (its own
@@ -1530,11 +1511,11 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
       const unsigned one = 1u;
       const int imax = 0x7fffffff;
       const unsigned long long umax = ~0ull;
-      if (!ck(hipMemsetAsync(vcounts, 0, 32 * sizeof(unsigned), s), "memset") ||
-          !ck(hipMemcpyAsync(vcounts, &one, sizeof one, hipMemcpyHostToDevice, s), "fallback") ||
-          !ck(hipMemcpyAsync(vfound, &imax, sizeof imax, hipMemcpyHostToDevice, s), "fallback") ||
-          !ck(hipMemcpyAsync(vbestk, &imax, sizeof imax, hipMemcpyHostToDevice, s), "fallback") ||
-          !ck(hipMemcpyAsync(val, &umax, sizeof umax, hipMemcpyHostToDevice, s), "fallback"))
+      if (!C.hip(hipMemsetAsync(vcounts, 0, 32 * sizeof(unsigned), s), "memset") ||
+          !C.hip(hipMemcpyAsync(vcounts, &one, sizeof one, hipMemcpyHostToDevice, s), "fallback") ||
+          !C.hip(hipMemcpyAsync(vfound, &imax, sizeof imax, hipMemcpyHostToDevice, s), "fallback") ||
+          !C.hip(hipMemcpyAsync(vbestk, &imax, sizeof imax, hipMemcpyHostToDevice, s), "fallback") ||
+          !C.hip(hipMemcpyAsync(val, &umax, sizeof umax, hipMemcpyHostToDevice, s), "fallback"))
         return false;
       VolArgs V = a;
       V.stuck_list = vstk_list;
@@ -1548,21 +1529,21 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
       E.list = vstk_list; E.count = vcounts; E.found = vfound; E.best = val; E.bestk = vbestk;
       E.spin_limit = 1L << 26;
       launch_exhaustive(E, V, fallback_blocks, s);
-      if (!ck(hipStreamSynchronize(s), "sync")) return false;
+      if (!C.hip(hipStreamSynchronize(s), "sync")) return false;
       unsigned derr = 0;
-      if (!ck(hipMemcpy(&derr, vcounts + PMX_CNT_ERR, sizeof derr, hipMemcpyDeviceToHost), "fallback")) return false;
+      if (!C.hip(hipMemcpy(&derr, vcounts + PMX_CNT_ERR, sizeof derr, hipMemcpyDeviceToHost), "fallback")) return false;
       if (derr) { err = "sequential replay: the one-point fallback's grid barrier timed out"; return false; }
       hctl[0] += 1;
       hctl[1] = -1;
       hctl[2] = 0;
-      if (!ck(hipMemcpyAsync(ctl + 4, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
+      if (!C.hip(hipMemcpyAsync(ctl + 4, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
     }
   }
   unsigned hr[2];
   int hn[2];
-  if (!ck(hipMemcpyAsync(hr, nreplay, sizeof hr, hipMemcpyDeviceToHost, s), "stats") ||
-      !ck(hipMemcpyAsync(hn, nseq, sizeof hn, hipMemcpyDeviceToHost, s), "stats") ||
-      !ck(hipStreamSynchronize(s), "sync"))
+  if (!C.hip(hipMemcpyAsync(hr, nreplay, sizeof hr, hipMemcpyDeviceToHost, s), "stats") ||
+      !C.hip(hipMemcpyAsync(hn, nseq, sizeof hn, hipMemcpyDeviceToHost, s), "stats") ||
+      !C.hip(hipStreamSynchronize(s), "sync"))
     return false;
   seq_stats[0] = surf ? hr[0] : 0;
   seq_stats[1] = surf ? (unsigned)hn[0] : 0;

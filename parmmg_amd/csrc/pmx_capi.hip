@@ -39,34 +39,20 @@ static std::atomic<int> &live_contexts(int device) {
 }
 void pmx_set_noctx_error(const char *msg) { noctx_err = msg; }
 
-static bool ok(pmx_ctx *c, hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  c->err = std::string(what) + ": " + hipGetErrorString(e);
-  return false;
-}
-#define CK(x) do { if (!ok(ctx, (x), #x)) return 0; } while (0)
+#define CK(x) PMX_CK(pmx_call{ctx}, x)
 
-template <class T> static bool dgrow(pmx_ctx *ctx, DevBuf<T> &b, size_t n) {
-  return pmx_dgrow(ctx, b, n);
-}
 // pinned staging of at least `bytes`, 25 % slack so that a slowly growing
 // ParMmg group does not re-pin every iteration.  Every arena copy is on the
 // context's stream and no call waits for its last one (pmx_upload_points
 // returns with its coordinates still in flight): the arena is handed out only
 // once that stream has drained, so no host write, read or re-pin races a DMA.
 char *pmx_hstage(pmx_ctx *ctx, size_t bytes) {
-  if (!ok(ctx, hipStreamSynchronize(ctx->stream), "pmx_hstage: stream")) return nullptr;
-  if (bytes <= ctx->h_stage_cap && ctx->h_stage) return (char *)ctx->h_stage;
-  if (ctx->h_stage) hipHostFree(ctx->h_stage);
-  ctx->h_stage = nullptr;
-  ctx->h_stage_cap = 0;
+  const pmx_call C{ctx};
+  if (!C.hip(hipStreamSynchronize(ctx->stream), "pmx_hstage: stream")) return nullptr;
   const size_t cap = std::max<size_t>(bytes + bytes / 4, 1 << 20);
-  if (!ok(ctx, hipHostMalloc(&ctx->h_stage, cap, hipHostMallocDefault), "hipHostMalloc")) return nullptr;
-  ctx->h_stage_cap = cap;
-  return (char *)ctx->h_stage;
+  if (!C.hip(ctx->h_stage.grow(bytes, cap), "hipHostMalloc")) return nullptr;
+  return ctx->h_stage.p;
 }
-static char *hstage(pmx_ctx *ctx, size_t bytes) { return pmx_hstage(ctx, bytes); }
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // The process's CPU share: the CPUs it may run on, capped by a cgroup v2 CPU
 // quota (cpu.max "quota period"; a GPU box of this pool: 16 of 256).
@@ -229,13 +215,13 @@ void pmx_par_for(int64_t lo, int64_t hi, const std::function<void(int64_t, int64
 
 bool pmx_download_qual(pmx_ctx *ctx, const double *dev, int64_t ne, double *qual, int64_t stride) {
   const bool dense = stride == (int64_t)sizeof(double);
-  const int4 *htv = (const int4 *)ctx->h_tets;
-  if (!dense && (!htv || ctx->h_tets_cap < (size_t)(ne + 1) * sizeof(int4))) {
+  const int4 *htv = (const int4 *)ctx->h_tets.p;
+  if (!dense && (!htv || ctx->h_tets.cap < (size_t)(ne + 1) * sizeof(int4))) {
     ctx->err = "qualities: strided output needs the new tets' host copy";
     return false;
   }
   hipStream_t s = ctx->stream;
-  char *st = hstage(ctx, (size_t)(ne + 1) * sizeof(double));
+  char *st = pmx_hstage(ctx, (size_t)(ne + 1) * sizeof(double));
   if (!st) return false;
   const double *h = (const double *)st;
   char *out = (char *)qual;
@@ -277,23 +263,11 @@ bool pmx_download_qual(pmx_ctx *ctx, const double *dev, int64_t ne, double *qual
 // the pinned copy of the new tets, ne + 1 records
 int4 *pmx_ctx::grow_htets(int64_t ne) {
   const size_t bytes = (size_t)(ne + 1) * sizeof(int4);
-  if (bytes > h_tets_cap) {
-    if (h_tets) hipHostFree(h_tets);
-    h_tets = nullptr;
-    h_tets_cap = 0;
-    if (hipHostMalloc((void **)&h_tets, bytes, hipHostMallocDefault) != hipSuccess) {
-      err = "pinned staging of the new tets";
-      return nullptr;
-    }
-    h_tets_cap = bytes;
+  if (h_tets.grow(bytes, bytes) != hipSuccess) {
+    err = "pinned staging of the new tets";
+    return nullptr;
   }
-  return (int4 *)h_tets;
-}
-
-template <class T> static void dfree(DevBuf<T> &b) {
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
+  return (int4 *)h_tets.p;
 }
 
 bool pmx_ctx::check_device_errors() {
@@ -409,19 +383,10 @@ pmx_ctx *pmx_create(int device) {
     sok = mk(&ctx->topo) && mk(&ctx->up) && mk(&ctx->own) && mk(&ctx->side);
   ctx->stream = ctx->own;
   if (!sok ||
-      hipEventCreateWithFlags(&ctx->ev_topo, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_tets, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void **)&ctx->h_nbad, 8 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
-      [&] {
-        for (auto &e : ctx->ev_dl)
-          if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return true;
-        for (auto &e : ctx->ev_eg)
-          if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return true;
-        return false;
-      }() ||
-      hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_fork2, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) {
+      !ctx->ev_topo.create(false) || !ctx->ev_tets.create(false) ||
+      ctx->h_nbad.grow(8 * sizeof(unsigned), 8 * sizeof(unsigned)) != hipSuccess ||
+      !pmx_create_events(ctx->ev_dl, false) || !pmx_create_events(ctx->ev_eg, false) ||
+      !ctx->ev_fork.create(false) || !ctx->ev_fork2.create(false) || !ctx->ev_join.create(false)) {
     pmx_destroy(ctx);
     return nullptr;
   }
@@ -451,29 +416,11 @@ void pmx_destroy(pmx_ctx *ctx) {
   if (ctx->side) hipStreamSynchronize(ctx->side);
   if (ctx->topo) hipStreamSynchronize(ctx->topo);
   if (ctx->up) hipStreamSynchronize(ctx->up);
-  ctx->free_all();
-  for (auto &e : ctx->events) hipEventDestroy(e);
-  for (auto &e : ctx->more_ev) hipEventDestroy(e);
-  for (auto &e : ctx->graph_ev) hipEventDestroy(e);
-  for (auto &e : ctx->contig_ev)
-    if (e) hipEventDestroy(e);
-  if (ctx->ev_fork) hipEventDestroy(ctx->ev_fork);
-  if (ctx->ev_fork2) hipEventDestroy(ctx->ev_fork2);
-  if (ctx->ev_join) hipEventDestroy(ctx->ev_join);
   if (ctx->side) hipStreamDestroy(ctx->side);
   if (ctx->topo) hipStreamDestroy(ctx->topo);
-  if (ctx->ev_topo) hipEventDestroy(ctx->ev_topo);
-  if (ctx->ev_tets) hipEventDestroy(ctx->ev_tets);
   if (ctx->up) hipStreamDestroy(ctx->up);
-  if (ctx->h_tets) hipHostFree(ctx->h_tets);
-  for (auto &e : ctx->ev_dl)
-    if (e) hipEventDestroy(e);
-  for (auto &e : ctx->ev_eg)
-    if (e) hipEventDestroy(e);
-  if (ctx->h_out) hipHostFree(ctx->h_out);
-  if (ctx->h_nbad) hipHostFree(ctx->h_nbad);
   if (ctx->own) hipStreamDestroy(ctx->own);
-  delete ctx;
+  delete ctx;                              // the device current, the streams drained: the members release themselves
 }
 
 const char *pmx_last_error(pmx_ctx *ctx) {
@@ -579,12 +526,12 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
   // adjacency) | packed hint sample | solutions; each part goes down as soon
   // as it is packed (the tets in chunks), one sync at the end
   const size_t trec = dev_adja ? sizeof(int4) : sizeof(TetRec);
-  const size_t o_p = 0, o_t = o_p + al256((size_t)(np + 1) * 24),
-               o_h = o_t + al256((size_t)(ne + 1) * trec),
-               o_s = o_h + al256(host_sample ? (size_t)ns * sizeof(int4) : 0),
-               total = o_s + al256(hs_n * sizeof(double));
+  const size_t o_p = 0, o_t = o_p + pmx_call::al256((size_t)(np + 1) * 24),
+               o_h = o_t + pmx_call::al256((size_t)(ne + 1) * trec),
+               o_s = o_h + pmx_call::al256(host_sample ? (size_t)ns * sizeof(int4) : 0),
+               total = o_s + pmx_call::al256(hs_n * sizeof(double));
   CK(hipStreamSynchronize(ctx->stream));   // the arena may still feed an earlier copy
-  char *stg = hstage(ctx, total);
+  char *stg = pmx_hstage(ctx, total);
   if (!stg) return 0;
   // any return after the topology fork first waits for that stream (a later
   // call may regrow the buffers its kernels use)
@@ -592,12 +539,12 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
     hipStream_t s = nullptr;
     ~StreamGuard() { if (s) hipStreamSynchronize(s); }
   } topo_guard;
-  if (!dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) || !dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) ||
-      (ctx->compact_recs && !dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !dgrow(ctx, ctx->d_wfar, 8) ||
-      !dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) || !dgrow(ctx, ctx->d_sol, hs_n) ||
-      !dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) || !dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) ||
-      !dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) ||
-      (dev_adja && (!dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) || !dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)))))
+  if (!pmx_dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) || !pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) ||
+      (ctx->compact_recs && !pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !pmx_dgrow(ctx, ctx->d_wfar, 8) ||
+      !pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) || !pmx_dgrow(ctx, ctx->d_sol, hs_n) ||
+      !pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) || !pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) ||
+      !pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) ||
+      (dev_adja && (!pmx_dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) || !pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)))))
     return 0;
   hipStream_t st = ctx->stream;
 
@@ -678,11 +625,11 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
     ctx->err = "pmx_upload_background: tet vertex or adjacency index out of range";
     return 0;
   }
-  ctx->h_nbad[2] = 0;                        // no far fields unless compact records are built
+  ctx->h_nbad.p[2] = 0;                        // no far fields unless compact records are built
   if (!dev_adja) {
     if (host_sample)
       CK(hipMemcpyAsync(ctx->d_tets_s.p, hh, (size_t)ns * sizeof(int4), hipMemcpyHostToDevice, st));
-    if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad + 2, st);
+    if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, st);
     // the owner sample (mode 2) while the host packs the solutions and trias
     if (!ctx->order_hint_samples(ne, np, st)) return 0;
   }
@@ -694,13 +641,13 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
     CK(hipEventRecord(ctx->ev_fork, st));
     CK(hipStreamWaitEvent(ctx->topo, ctx->ev_fork, 0));
     topo_guard.s = ctx->topo;
-    ctx->h_nbad[1] = 0;                      // [0] belongs to a pending residency build
-    if (!pmx_ctx_build_adja_device(ctx, ctx->d_btv.p, ne, np, ctx->d_adja.p, ctx->topo, ctx->h_nbad + 1))
+    ctx->h_nbad.p[1] = 0;                      // [0] belongs to a pending residency build
+    if (!pmx_ctx_build_adja_device(ctx, ctx->d_btv.p, ne, np, ctx->d_adja.p, ctx->topo, ctx->h_nbad.p + 1))
       return 0;
     launch_build_tetrec(ctx->d_btv.p, ctx->d_adja.p, ne, PMX_HINT_STRIDE, ctx->d_tets.p, ctx->d_tets_s.p,
                         ctx->topo);
     if (ctx->compact_recs)
-      launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad + 2, ctx->topo);
+      launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, ctx->topo);
     if (!ctx->order_hint_samples(ne, np, ctx->topo)) return 0;
     CK(hipEventRecord(ctx->ev_join, ctx->topo));
   }
@@ -754,12 +701,12 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
   tr.mark("trias + topology");
   CK(hipStreamSynchronize(ctx->stream));   // host staging vectors die here
   tr.mark("sync");
-  if (dev_adja && ctx->h_nbad[1]) {
+  if (dev_adja && ctx->h_nbad.p[1]) {
     ctx->err = "pmx_upload_background: non-manifold tet faces";
     return 0;
   }
-  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad[4] == 0;
-  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad[5] : 0;
+  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad.p[4] == 0;
+  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[5] : 0;
   ctx->bg_btv = dev_adja;
   ctx->have_bg = true;
   return 1;
@@ -804,19 +751,19 @@ int pmx_upload_points(pmx_ctx *ctx, const pmx_points_view *pv) {
   // (src/interpmesh_pmmg.c:535-560).  The host's tag pass gives the launch
   // sizes (upper bounds: orphans are found on the device).
   const int64_t ntet = pv->tetra_v ? pv->ne : 0;
-  const size_t o_x = 0, o_tg = o_x + al256(nn * 3 * sizeof(double)),
-               total = o_tg + al256(pv->tag ? nn * 2 : 0);
+  const size_t o_x = 0, o_tg = o_x + pmx_call::al256(nn * 3 * sizeof(double)),
+               total = o_tg + pmx_call::al256(pv->tag ? nn * 2 : 0);
   CK(hipStreamSynchronize(ctx->stream));   // the arena may still feed an earlier copy
-  char *st = hstage(ctx, total);
+  char *st = pmx_hstage(ctx, total);
   if (!st) return 0;
   double *hx = (double *)(st + o_x);
   uint16_t *htg = (uint16_t *)(st + o_tg);
   const char *pc = (const char *)pv->c;
   const char *tg = (const char *)pv->tag;
-  if (!dgrow(ctx, ctx->d_qxyz, nn * 3) || !dgrow(ctx, ctx->d_kind, nn) || !dgrow(ctx, ctx->d_qmark, nn + 64) ||   // + 64: the marks' word-wide flush
-      !dgrow(ctx, ctx->d_nsel, 2) || !dgrow(ctx, ctx->d_vollist, nn) || !dgrow(ctx, ctx->d_bdylist, nn) ||
-      !dgrow(ctx, ctx->d_ctile, (size_t)std::max<int64_t>(cls_tiles(n), 1)) ||
-      (tg && !dgrow(ctx, ctx->d_qtag, nn)) || (ntet && !dgrow(ctx, ctx->d_ntetv, (size_t)(ntet + 1))))
+  if (!pmx_dgrow(ctx, ctx->d_qxyz, nn * 3) || !pmx_dgrow(ctx, ctx->d_kind, nn) || !pmx_dgrow(ctx, ctx->d_qmark, nn + 64) ||   // + 64: the marks' word-wide flush
+      !pmx_dgrow(ctx, ctx->d_nsel, 2) || !pmx_dgrow(ctx, ctx->d_vollist, nn) || !pmx_dgrow(ctx, ctx->d_bdylist, nn) ||
+      !pmx_dgrow(ctx, ctx->d_ctile, (size_t)std::max<int64_t>(cls_tiles(n), 1)) ||
+      (tg && !pmx_dgrow(ctx, ctx->d_qtag, nn)) || (ntet && !pmx_dgrow(ctx, ctx->d_ntetv, (size_t)(ntet + 1))))
     return 0;
   // coordinates (+ bounding box: a promoted background's hint grid) and tags
   // (+ the per-path upper bounds)
@@ -868,30 +815,30 @@ int pmx_upload_points(pmx_ctx *ctx, const pmx_points_view *pv) {
   ctx->tets_pending = ntet > 0;
   ctx->view_tets = ntet > 0;
   ctx->nq = n;
-  if (!dgrow(ctx, ctx->d_wmask, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_elem, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_status, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_steps, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_wmask, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_elem, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_status, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_steps, nn)) return 0;
   // points a step never locates (NUL, frozen, orphans) report element 0
   CK(hipMemsetAsync(ctx->d_elem.p, 0, nn * sizeof(int), ctx->stream));
   CK(hipMemsetAsync(ctx->d_status.p, 0, nn * sizeof(int), ctx->stream));
   CK(hipMemsetAsync(ctx->d_steps.p, 0, nn * sizeof(int), ctx->stream));
-  if (!dgrow(ctx, ctx->d_start, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_edge, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_vertex, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_start, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_edge, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_vertex, nn)) return 0;
   // start 0, edge / vertex unset (-1) for every point no step writes
   CK(hipMemsetAsync(ctx->d_start.p, 0, nn * sizeof(int), ctx->stream));
   CK(hipMemsetAsync(ctx->d_edge.p, 0xff, nn * sizeof(int), ctx->stream));
   CK(hipMemsetAsync(ctx->d_vertex.p, 0xff, nn * sizeof(int), ctx->stream));
-  if (!dgrow(ctx, ctx->d_list, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_found, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_bestk, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_best, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_ties, nn)) return 0;
-  if (!dgrow(ctx, ctx->d_counts, 32)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_list, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_found, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_bestk, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_best, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_ties, nn)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_counts, 32)) return 0;
   // one record per wave (sized for every point on one path)
-  if (!dgrow(ctx, ctx->d_vstat, (nn + 255) / 256 * 4 + 4)) return 0;
-  if (!dgrow(ctx, ctx->d_bstat, (nn + 255) / 256 * 4 + 4)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_vstat, (nn + 255) / 256 * 4 + 4)) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_bstat, (nn + 255) / 256 * 4 + 4)) return 0;
   // no wait for the copies: the step queues behind them, and the next host
   // use of the arena waits for the stream (pmx_hstage)
   ctx->have_qtag = tg && n;
@@ -918,9 +865,9 @@ int pmx_upload_point_sources(pmx_ctx *ctx, const int *src, int64_t stride) {
   if (stride < (int64_t)sizeof(int)) { ctx->err = "pmx_upload_point_sources: bad stride"; return 0; }
   hipSetDevice(ctx->device);
   const int64_t n = ctx->nq;
-  if (!dgrow(ctx, ctx->d_qsrc, (size_t)std::max<int64_t>(n, 1))) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_qsrc, (size_t)std::max<int64_t>(n, 1))) return 0;
   if (n) {
-    int *h = (int *)hstage(ctx, (size_t)n * sizeof(int));
+    int *h = (int *)pmx_hstage(ctx, (size_t)n * sizeof(int));
     if (!h) return 0;
     const char *ps = (const char *)src;
     const int64_t first = ctx->pts_first;
@@ -999,16 +946,16 @@ bool pmx_ctx::pack_new_tets() {
   // the download go on
   if (residency && ntet > 0) {
     const int64_t ns = (ntet + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
-    if (!dgrow(this, d_adja, (size_t)(4 * ntet + 5)) || !dgrow(this, d_tets_next, (size_t)(ntet + 1)) ||
-        (compact_recs && !dgrow(this, d_wrec_next, (size_t)(ntet + 1))) || !dgrow(this, d_wfar, 8) ||
-        !dgrow(this, d_tets_s_next, (size_t)std::max<int64_t>(ns, 1)))
+    if (!pmx_dgrow(this, d_adja, (size_t)(4 * ntet + 5)) || !pmx_dgrow(this, d_tets_next, (size_t)(ntet + 1)) ||
+        (compact_recs && !pmx_dgrow(this, d_wrec_next, (size_t)(ntet + 1))) || !pmx_dgrow(this, d_wfar, 8) ||
+        !pmx_dgrow(this, d_tets_s_next, (size_t)std::max<int64_t>(ns, 1)))
       return false;
-    *h_nbad = 0;
+    *h_nbad.p = 0;
     CK(hipStreamWaitEvent(topo, ev_tets, 0));
-    if (!pmx_ctx_build_adja_device(this, d_ntetv.p, ntet, n, d_adja.p, topo, h_nbad)) return false;
+    if (!pmx_ctx_build_adja_device(this, d_ntetv.p, ntet, n, d_adja.p, topo, h_nbad.p)) return false;
     launch_build_tetrec(d_ntetv.p, d_adja.p, ntet, PMX_HINT_STRIDE, d_tets_next.p, d_tets_s_next.p, topo);
-    h_nbad[3] = 0;
-    if (compact_recs) launch_build_wrec(d_tets_next.p, ntet, d_wrec_next.p, d_wfar.p + 1, h_nbad + 3, topo);
+    h_nbad.p[3] = 0;
+    if (compact_recs) launch_build_wrec(d_tets_next.p, ntet, d_wrec_next.p, d_wfar.p + 1, h_nbad.p + 3, topo);
     CK(hipEventRecord(ev_topo, topo));
     next_topo = true;
   }
@@ -1050,12 +997,12 @@ bool pmx_ctx::order_hint_samples(int64_t ne, int64_t np, hipStream_t s) {
   samples_sorted = samples_owner = false;
   if (sample_mode != 2 || np < 1 || ne < 1) return true;
   const size_t tb = owner_scan_temp_bytes(np);
-  if (!dgrow(this, d_skey, (size_t)(np + 2)) || !dgrow(this, d_sidx, (size_t)(2 * (np + 1))) ||
-      !dgrow(this, d_salt, (size_t)(np + 1)) || !dgrow(this, d_tets_sk, (size_t)(np + 1)) ||
-      !dgrow(this, d_stmp, std::max<size_t>(tb, 1)) || !dgrow(this, d_wfar, 8))
+  if (!pmx_dgrow(this, d_skey, (size_t)(np + 2)) || !pmx_dgrow(this, d_sidx, (size_t)(2 * (np + 1))) ||
+      !pmx_dgrow(this, d_salt, (size_t)(np + 1)) || !pmx_dgrow(this, d_tets_sk, (size_t)(np + 1)) ||
+      !pmx_dgrow(this, d_stmp, std::max<size_t>(tb, 1)) || !pmx_dgrow(this, d_wfar, 8))
     return false;
   if (!launch_owner_sample(d_tets.p, ne, np, d_skey.p, d_sidx.p, d_sidx.p + (np + 1), d_salt.p, d_tets_sk.p,
-                           d_wfar.p + 4, h_nbad + 5, d_stmp.p, tb, s)) {
+                           d_wfar.p + 4, h_nbad.p + 5, d_stmp.p, tb, s)) {
     err = "hint sample: vertex owners";
     return false;
   }
@@ -1073,10 +1020,10 @@ bool pmx_ctx::rederive(hipStream_t s) {
   if (bg_btv) {
     // face matching of the uploaded connectivity, then the tet records and
     // the every-4th-tet sample (MMG3D_hashTetra's adjacency on the device)
-    if (!pmx_ctx_build_adja_device(this, d_btv.p, ne, np, d_adja.p, s, h_nbad + 1)) return false;
+    if (!pmx_ctx_build_adja_device(this, d_btv.p, ne, np, d_adja.p, s, h_nbad.p + 1)) return false;
     launch_build_tetrec(d_btv.p, d_adja.p, ne, PMX_HINT_STRIDE, d_tets.p, d_tets_s.p, s);
   }
-  if (compact_recs) launch_build_wrec(d_tets.p, ne, d_wrec.p, d_wfar.p, h_nbad + 2, s);
+  if (compact_recs) launch_build_wrec(d_tets.p, ne, d_wrec.p, d_wfar.p, h_nbad.p + 2, s);
   if (sample_mode == 2 && !order_hint_samples(ne, np, s)) return false;
   CK(hipGetLastError());
   return true;
@@ -1117,9 +1064,9 @@ static void fill_vol_args(pmx_ctx *ctx, const SolDesc &sd, const pmx_run_opts &o
   // faster; 9 %, 32-B 1.5 % faster; appended 41 %, 32-B 5.5 % faster --
   // DESIGN.md section 7).  exp 18: compact records always
   if (!ctx->compact_recs ||
-      (A.exp != 18 && (uint64_t)ctx->h_nbad[2] * PMX_WREC_FAR_DIV > (uint64_t)std::max<int64_t>(ctx->ne, 1)))
+      (A.exp != 18 && (uint64_t)ctx->h_nbad.p[2] * PMX_WREC_FAR_DIV > (uint64_t)std::max<int64_t>(ctx->ne, 1)))
     A.wrec = nullptr;
-  A.far = ctx->h_nbad[2] > 0 ? 1 : 0;
+  A.far = ctx->h_nbad.p[2] > 0 ? 1 : 0;
   // point-map starts: no grid; the walks' PM instantiations read the start
   // elements the classification resolved, passed in its place
   if (opts.flags & PMX_RUN_POINTMAP) A.grid = ctx->d_pstart.p;
@@ -1169,16 +1116,16 @@ int pmx_run(pmx_ctx *ctx, const pmx_run_opts *o) {
     return 0;
   }
   const int64_t n = ctx->nq;
-  if (pm && (!dgrow(ctx, ctx->d_pstart, (size_t)std::max<int64_t>(2 * n, 1)) ||
-             !dgrow(ctx, ctx->d_pmap, (size_t)(2 * (ctx->np + 1))) || !dgrow(ctx, ctx->d_pmcnt, 2)))
+  if (pm && (!pmx_dgrow(ctx, ctx->d_pstart, (size_t)std::max<int64_t>(2 * n, 1)) ||
+             !pmx_dgrow(ctx, ctx->d_pmap, (size_t)(2 * (ctx->np + 1))) || !pmx_dgrow(ctx, ctx->d_pmcnt, 2)))
     return 0;
   const int S = ctx->sd.S;
-  if (!dgrow(ctx, ctx->d_out, (size_t)std::max<int64_t>(n * S, 1))) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_out, (size_t)std::max<int64_t>(n * S, 1))) return 0;
   SolDesc sd = ctx->sd;
   sd.metric_const = (opts.hsiz > 0.0 && sd.imet >= 0) ? 1 : 0;
 
-  hipEvent_t *ev = nullptr;
-  if (opts.timing) ev = ctx->next_event_slot();
+  DevEvent *ev = nullptr;
+  if (opts.timing && !(ev = ctx->next_event_slot())) return 0;
 
   hipStream_t st = ctx->stream;
   // everything below is one iteration's device work on the uploaded raw
@@ -1361,24 +1308,20 @@ bool pmx_ctx::eager_download() {
   const int64_t n = nq;
   const int S = sd.S;
   if (n == 0 || S == 0) return true;
-  const size_t o_wm = al256((size_t)(n * S) * sizeof(double)), bytes = o_wm + al256((size_t)n);
-  if (bytes > h_out_cap) {
+  const size_t o_wm = pmx_call::al256((size_t)(n * S) * sizeof(double)), bytes = o_wm + pmx_call::al256((size_t)n);
+  if (bytes > h_out.cap) {
     CK(hipStreamSynchronize(stream));      // an earlier eager copy may still land in it
-    if (h_out) hipHostFree(h_out);
-    h_out = nullptr;
-    h_out_cap = 0;
-    if (hipHostMalloc((void **)&h_out, bytes + bytes / 4, hipHostMallocDefault) != hipSuccess) {
+    if (h_out.grow(bytes, bytes + bytes / 4) != hipSuccess) {
       err = "pmx_run: pinned staging of the eager download";
       return false;
     }
-    h_out_cap = bytes + bytes / 4;
   }
   const int nch = (int)std::max<int64_t>(1, std::min<int64_t>(4, (n * S) >> 21));
   for (int c = 0; c < nch; c++) {
     const int64_t lo = n * c / nch, hi = n * (c + 1) / nch;
-    CK(hipMemcpyAsync(h_out + (size_t)(lo * S) * sizeof(double), d_out.p + lo * S,
+    CK(hipMemcpyAsync(h_out.p + (size_t)(lo * S) * sizeof(double), d_out.p + lo * S,
                       (size_t)((hi - lo) * S) * sizeof(double), hipMemcpyDeviceToHost, stream));
-    CK(hipMemcpyAsync(h_out + o_wm + lo, d_wmask.p + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, stream));
+    CK(hipMemcpyAsync(h_out.p + o_wm + lo, d_wmask.p + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, stream));
     CK(hipEventRecord(ev_eg[c], stream));
   }
   eager_nch = nch;
@@ -1432,8 +1375,8 @@ static void scatter_rows(const pmx_ctx *ctx, const pmx_sol_view *new_sols, const
 static int download_eager(pmx_ctx *ctx, const pmx_sol_view *new_sols, int *elem, int *status, int *steps) {
   const int64_t n = ctx->nq;
   const int S = ctx->sd.S;
-  const double *h = (const double *)ctx->h_out;
-  const uint8_t *wm = (const uint8_t *)(ctx->h_out + al256((size_t)(n * S) * sizeof(double)));
+  const double *h = (const double *)ctx->h_out.p;
+  const uint8_t *wm = (const uint8_t *)(ctx->h_out.p + pmx_call::al256((size_t)(n * S) * sizeof(double)));
   // the eager copy holds the step's masks; with new tets, the orphan reset
   // (fix_orphans, enqueued by pmx_download after them) changed some: take the
   // masks again (n bytes)
@@ -1442,11 +1385,11 @@ static int download_eager(pmx_ctx *ctx, const pmx_sol_view *new_sols, int *elem,
     CK(hipStreamSynchronize(ctx->stream));
   }
   const bool want_int = elem || status || steps;
-  const size_t o_el = 0, o_st = o_el + al256((size_t)n * sizeof(int)), o_sp = o_st + al256((size_t)n * sizeof(int)),
-               total = o_sp + al256((size_t)n * sizeof(int));
+  const size_t o_el = 0, o_st = o_el + pmx_call::al256((size_t)n * sizeof(int)), o_sp = o_st + pmx_call::al256((size_t)n * sizeof(int)),
+               total = o_sp + pmx_call::al256((size_t)n * sizeof(int));
   char *st = nullptr;
   if (want_int) {
-    st = hstage(ctx, total);               // waits for the stream: the eager chunks have landed
+    st = pmx_hstage(ctx, total);               // waits for the stream: the eager chunks have landed
     if (!st) return 0;
     if (elem) CK(hipMemcpyAsync(st + o_el, ctx->d_elem.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (status) CK(hipMemcpyAsync(st + o_st, ctx->d_status.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1493,10 +1436,10 @@ int pmx_download(pmx_ctx *ctx, const pmx_sol_view *new_sols, int64_t npts_cap, i
   // then the host scatters into the caller's (pageable, strided) arrays
   const bool want_sol = new_sols && S > 0;
   if (want_sol && ctx->eager_nch > 0) return download_eager(ctx, new_sols, elem, status, steps);
-  const size_t o_out = 0, o_wm = o_out + al256(want_sol ? (size_t)(n * S) * sizeof(double) : 0),
-               o_el = o_wm + al256(want_sol ? (size_t)n : 0), o_st = o_el + al256((size_t)n * sizeof(int)),
-               o_sp = o_st + al256((size_t)n * sizeof(int)), total = o_sp + al256((size_t)n * sizeof(int));
-  char *st = hstage(ctx, total);
+  const size_t o_out = 0, o_wm = o_out + pmx_call::al256(want_sol ? (size_t)(n * S) * sizeof(double) : 0),
+               o_el = o_wm + pmx_call::al256(want_sol ? (size_t)n : 0), o_st = o_el + pmx_call::al256((size_t)n * sizeof(int)),
+               o_sp = o_st + pmx_call::al256((size_t)n * sizeof(int)), total = o_sp + pmx_call::al256((size_t)n * sizeof(int));
+  char *st = pmx_hstage(ctx, total);
   if (!st) return 0;
   const double *h = (const double *)(st + o_out);
   const uint8_t *wm = (const uint8_t *)(st + o_wm);
@@ -1718,6 +1661,8 @@ int64_t pmx_debug_hint_grid(pmx_ctx *ctx, int *host, int64_t cap) {
   return ctx->gcells;
 }
 
+int64_t pmx_debug_live_allocations(void) { return pmx_live_allocations.load(std::memory_order_relaxed); }
+
 int pmx_pointmap_stats(pmx_ctx *ctx, int64_t atomics[2]) {
   if (!ctx || !atomics) return 0;
   if (!ctx->have_pmap) { ctx->err = "pmx_pointmap_stats: no PMX_RUN_POINTMAP step on this background"; return 0; }
@@ -1745,7 +1690,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
   for (int r = 0; r < ctx->ev_used; r++) {
-    hipEvent_t *e = &ctx->events[(size_t)r * PMX_EV_PER_RUN];
+    const DevEvent *e = &ctx->events[(size_t)r * PMX_EV_PER_RUN];
     float ms = 0.f;
     // 0 hint (prologue + derived data + hint build), 1 volume walk, 2 surface
     // path, 3 fallback, 4 total, 5 derived data (prologue included), 6 the
@@ -1790,7 +1735,7 @@ int pmx_upload_new_tets(pmx_ctx *ctx, const int *tetra_v, int64_t tetra_stride, 
       CK(hipEventSynchronize(ctx->ev_tets));
       ctx->tets_inflight = false;
     }
-    const int4 *old = (const int4 *)ctx->h_tets;
+    const int4 *old = (const int4 *)ctx->h_tets.p;
     bool same = old && !ctx->tets_pending && ne == ctx->tview.ne;
     const char *tc0 = (const char *)tetra_v;
     for (int64_t k = 1; same && k <= ne; k++) {
@@ -1848,7 +1793,7 @@ int pmx_upload_new_tets(pmx_ctx *ctx, const int *tetra_v, int64_t tetra_stride, 
     std::atomic_thread_fence(std::memory_order_seq_cst);
   });
   if (bad) { ctx->err = "pmx_upload_new_tets: tet vertex outside the uploaded points"; return 0; }
-  if (!dgrow(ctx, ctx->d_ntetv, (size_t)(ne + 1))) return 0;
+  if (!pmx_dgrow(ctx, ctx->d_ntetv, (size_t)(ne + 1))) return 0;
   CK(hipMemcpyAsync(ctx->d_ntetv.p, h, (size_t)(ne + 1) * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
   if (ctx->view_tets && n > 0) {
     // these tets replace the points view's: the reference visits the points
@@ -1925,7 +1870,7 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   const int S = sd.S;
   // rows the step did not write keep the caller's values (Mmg's own, or the
   // frozen-point copy): which ones, from the write masks
-  char *stg = hstage(ctx, (size_t)n);
+  char *stg = pmx_hstage(ctx, (size_t)n);
   if (!stg) return 0;
   CK(hipMemcpyAsync(stg, ctx->d_wmask.p, (size_t)n, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
@@ -1970,17 +1915,17 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   ctx->bg_btv = false;                     // records from the new tets (or the caller's adja), not d_btv
   ctx->stat_np = -1;
   const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
-  if (!dgrow(ctx, ctx->d_xyz, (size_t)(n + 1) * 3) || !dgrow(ctx, ctx->d_sol, (size_t)(n + 1) * std::max(S, 1)) ||
-      !dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) || !dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) ||
-      !dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)) || !dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) ||
-      !dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) || !dgrow(ctx, ctx->d_xyzq, (size_t)(n + 1)))
+  if (!pmx_dgrow(ctx, ctx->d_xyz, (size_t)(n + 1) * 3) || !pmx_dgrow(ctx, ctx->d_sol, (size_t)(n + 1) * std::max(S, 1)) ||
+      !pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) || !pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) ||
+      !pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)) || !pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) ||
+      !pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) || !pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(n + 1)))
     return 0;
   const bool tags = ctx->have_qtag;
-  if (tags && !dgrow(ctx, ctx->d_ptag, (size_t)(n + 1))) return 0;
+  if (tags && !pmx_dgrow(ctx, ctx->d_ptag, (size_t)(n + 1))) return 0;
   launch_promote(ctx->d_qxyz.p, ctx->d_out.p, tags ? ctx->d_qtag.p : nullptr, n, S, ctx->d_xyz.p, ctx->d_sol.p,
                  tags ? ctx->d_ptag.p : nullptr, st);
   if (!ent.empty()) {
-    if (!dgrow(ctx, ctx->d_pent, ent.size()) || !dgrow(ctx, ctx->d_pval, vals.size())) return 0;
+    if (!pmx_dgrow(ctx, ctx->d_pent, ent.size()) || !pmx_dgrow(ctx, ctx->d_pval, vals.size())) return 0;
     CK(hipMemcpyAsync(ctx->d_pent.p, ent.data(), ent.size() * sizeof(int4), hipMemcpyHostToDevice, st));
     CK(hipMemcpyAsync(ctx->d_pval.p, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice, st));
     launch_patch_rows(ctx->d_pent.p, ctx->d_pval.p, (int64_t)ent.size(), S, ctx->d_sol.p, st);
@@ -1995,10 +1940,10 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
     ctx->next_topo = false;
   }
   if (prepared && !m->adja) {
-    if (*ctx->h_nbad) { ctx->err = "pmx_promote_background: non-manifold tet faces"; return 0; }
+    if (*ctx->h_nbad.p) { ctx->err = "pmx_promote_background: non-manifold tet faces"; return 0; }
     std::swap(ctx->d_tets, ctx->d_tets_next);
     std::swap(ctx->d_wrec, ctx->d_wrec_next);
-    ctx->h_nbad[2] = ctx->h_nbad[3];
+    ctx->h_nbad.p[2] = ctx->h_nbad.p[3];
     std::swap(ctx->d_tets_s, ctx->d_tets_s_next);
   } else {
     if (m->adja) {
@@ -2006,10 +1951,10 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
     } else if (!pmx_ctx_build_adja_device(ctx, ctx->d_ntetv.p, ne, n, ctx->d_adja.p, st, nullptr)) {
       return 0;
     }
-    if ((ctx->compact_recs && !dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !dgrow(ctx, ctx->d_wfar, 8)) return 0;
+    if ((ctx->compact_recs && !pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !pmx_dgrow(ctx, ctx->d_wfar, 8)) return 0;
     launch_build_tetrec(ctx->d_ntetv.p, ctx->d_adja.p, ne, PMX_HINT_STRIDE, ctx->d_tets.p, ctx->d_tets_s.p, st);
-    ctx->h_nbad[2] = 0;
-    if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad + 2, st);
+    ctx->h_nbad.p[2] = 0;
+    if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, st);
   }
   ctx->np = n;
   ctx->ne = ne;
@@ -2023,8 +1968,8 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   if (!ctx->check_fans(st)) return 0;
   CK(hipGetLastError());
   CK(hipStreamSynchronize(st));            // host vectors die here
-  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad[4] == 0;
-  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad[5] : 0;
+  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad.p[4] == 0;
+  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[5] : 0;
   tr.mark("uploads + sync");
   ctx->have_ptag = tags;
   // the points and the results were consumed: the next step needs new points
@@ -2056,55 +2001,18 @@ bool pmx_ctx::classify(hipStream_t s, bool marks, bool pointmap) {
   return true;
 }
 
-hipEvent_t *pmx_ctx::next_event_slot() {
+DevEvent *pmx_ctx::next_event_slot() {
   size_t need = (size_t)(ev_used + 1) * PMX_EV_PER_RUN;
-  while (events.size() < need) {
-    hipEvent_t e;
-    hipEventCreate(&e);
-    events.push_back(e);
-  }
-  hipEvent_t *r = &events[(size_t)ev_used * PMX_EV_PER_RUN];
+  if (events.size() < need) events.resize(need);
+  DevEvent *r = &events[(size_t)ev_used * PMX_EV_PER_RUN];
+  for (int k = 0; k < PMX_EV_PER_RUN; k++)
+    if (!r[k].create()) {
+      err = "pmx_run: creating the timing events failed";
+      return nullptr;
+    }
   ev_used++;
   return r;
 }
 
-void pmx_ctx::free_all() {
-  if (h_stage) hipHostFree(h_stage);
-  h_stage = nullptr;
-  h_stage_cap = 0;
-  dfree(d_xyz); dfree(d_tets); dfree(d_wrec); dfree(d_wrec_next); dfree(d_wfar); dfree(d_skey); dfree(d_sidx); dfree(d_salt); dfree(d_stmp); dfree(d_tets_sk); dfree(d_sol); dfree(d_tets_s); dfree(d_tris);
-  dfree(d_ntlist); dfree(d_ntval); dfree(d_ntkey); dfree(d_ntrange); dfree(d_nttmp); dfree(d_xyzq); dfree(d_trn); dfree(d_grid); dfree(d_tetv);
-  dfree(d_kind); dfree(d_qmark); dfree(d_ctile); dfree(d_nsel); dfree(d_wmask); dfree(d_out); dfree(d_elem); dfree(d_status);
-  dfree(d_steps); dfree(d_start); dfree(d_edge); dfree(d_vertex); dfree(d_list); dfree(d_found);
-  dfree(d_bestk); dfree(d_best); dfree(d_ties); dfree(d_counts); dfree(d_vollist); dfree(d_bdylist);
-  dfree(d_vstat); dfree(d_bstat);
-  dfree(d_bphi); dfree(d_msol); dfree(d_mout); dfree(d_mwm);
-  dfree(d_qsrc); dfree(d_pstart); dfree(d_pmap); dfree(d_pmcnt);
-  have_src = have_pmap = false;
-  dfree(d_sqkey); dfree(d_sqidx); dfree(d_sqint); dfree(d_sqtf); dfree(d_sqpf); dfree(d_sqtv); dfree(d_sqows); dfree(d_sqval);
-  dfree(d_sqw);
-  dfree(d_sqtmp);
-  dfree(d_sqflag);
-  dfree(d_sqcand);
-  dfree(d_qual); dfree(d_red); dfree(d_blist); dfree(d_olist); dfree(d_ows);
-  dfree(d_ptag); dfree(d_touch); dfree(d_cidx); dfree(d_intv); dfree(d_pub); dfree(d_pkey);
-  dfree(d_ppt); dfree(d_pedge); dfree(d_ntetv); dfree(d_nqual); dfree(d_qtag); dfree(d_gather);
-  dfree(d_adja); dfree(d_tcnt); dfree(d_toff); dfree(d_tbad); dfree(d_trec); dfree(d_ttmp);
-  dfree(d_pent); dfree(d_pval); dfree(d_tets_next); dfree(d_tets_s_next);
-  next_topo = false;
-  dfree(d_cmet); dfree(d_cperm); dfree(d_ccnt);
-  if (d_tgrid) hipFree(d_tgrid);
-  d_tgrid = nullptr;
-  d_tgrid_cap = 0;
-  have_bg = have_pts = ran = have_derived = have_tetv = have_qual = have_ptag = have_qtag = have_csr = false;
-  have_surf = false;
-  dfree(d_etag); dfree(d_pn); dfree(d_xpn); dfree(d_pxp); dfree(d_pedge_tag);
-  dfree(d_gdeg); dfree(d_gxadj); dfree(d_gadj); dfree(d_gwgt); dfree(d_gface); dfree(d_gflag); dfree(d_gtmp); dfree(d_gfw);
-  graph_ev_n = 0;
-  dfree(d_cpar); dfree(d_cmark); dfree(d_cstamp); dfree(d_cqueue); dfree(d_ctab); dfree(d_crec); dfree(d_crecol); dfree(d_cctl);
-  contig_label_ms = contig_replay_ms = -1.0;
-  pmx_split_free(this);
-  have_ntet = false;
-  stat_np = -1;
-}
+pmx_ctx::~pmx_ctx() { pmx_split_free(this); }
 

@@ -270,30 +270,24 @@ __global__ __launch_bounds__(256) void k_cc_recolour(int64_t ne, const int *__re
 
 struct Comp { int head, colour, size, open; };
 
-struct Contig {
-  pmx_ctx *ctx;
-  const char *who;
-  int64_t ne;
-  hipStream_t s;
-  unsigned nb;                 // blocks of 256 over the tets 1..ne
+struct Contig : pmx_call {
+  int64_t ne = 0;
+  unsigned nb = 0;             // blocks of 256 over the tets 1..ne
   std::vector<Comp> tab;       // sorted by (colour, head)
   int64_t rounds = 0;
-
-  bool fail(const std::string &what) { ctx->err = std::string(who) + ": " + what; return false; }
+  Contig(pmx_ctx *c, const char *w) : pmx_call{c, w, c->stream} {}
 
   // the refusals shared with pmx_metis_graph, the buffers, the events
   bool begin() {
     if (!ctx->have_bg) return fail("upload a group first");
     if (4 * ctx->ne >= (1LL << 31)) return fail("4 ne >= 2^31 (32-bit idx_t)");
     ne = ctx->ne;
-    s = ctx->stream;
-    nb = (unsigned)std::max<int64_t>((ne + 255) / 256, 1);
+    nb = blocks(ne);
     const size_t n = (size_t)(ne + 1);
     if (!pmx_dgrow(ctx, ctx->d_cpar, n) || !pmx_dgrow(ctx, ctx->d_cmark, n) || !pmx_dgrow(ctx, ctx->d_cstamp, n) ||
         !pmx_dgrow(ctx, ctx->d_cqueue, n) || !pmx_dgrow(ctx, ctx->d_cctl, CC_NCTL))
       return false;
-    for (auto &e : ctx->contig_ev)
-      if (!e && hipEventCreate(&e) != hipSuccess) return fail("event");
+    if (!pmx_create_events(ctx->contig_ev)) return fail("event");
     ctx->contig_label_ms = ctx->contig_replay_ms = 0.0;
     return true;
   }
@@ -307,12 +301,7 @@ struct Contig {
     ms += t;
     return true;
   }
-  bool read_ctl(unsigned *h) {
-    if (hipMemcpyAsync(h, ctx->d_cctl.p, sizeof(unsigned) * CC_NCTL, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return fail("control words");
-    return true;
-  }
+  bool read_ctl(unsigned *h) { return read_words(h, (const unsigned *)ctx->d_cctl.p, CC_NCTL); }
 
   // marks from the host's part (tet k at k - 1), or one colour
   bool set_marks(const int32_t *part) {

@@ -7,11 +7,7 @@
 #include <vector>
 #include "pmx_transfer.h"
 #include "pmx_kernels.h"
-
-template <class T> struct DevBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-};
+#include "pmx_host.h"
 
 // hint grid from every 4th tet: 1/4 of the stores and of the tet bytes of a
 // full build, at ~0.5 extra walk step (r01 measurements)
@@ -28,8 +24,8 @@ struct pmx_ctx {
   // the surface path runs on `side`, forked once the points are classified
   // and joined before the fallback: it overlaps the hint build and the volume walk
   hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_fork2 = nullptr, ev_join = nullptr;
-  hipEvent_t ev_dl[8] = {};             // chunked download: one per chunk
+  DevEvent ev_fork, ev_fork2, ev_join;
+  DevEvent ev_dl[8];                    // chunked download: one per chunk
   std::string err;
   int fallback_blocks = 0;              // co-resident k_fallback workgroups
   int fallback_share = 0;               // live contexts on the device they were sized for
@@ -38,8 +34,7 @@ struct pmx_ctx {
   pmx_ctx *peer = nullptr;
   // pinned host staging arena (hipHostMalloc, grown on demand, reused across
   // steps): uploads and downloads go through it as async DMA
-  void *h_stage = nullptr;
-  size_t h_stage_cap = 0;
+  PinBuf<char> h_stage;
 
   // background group (raw uploads)
   bool have_bg = false;
@@ -125,7 +120,7 @@ struct pmx_ctx {
   bool located = false;
   DevBuf<double> d_msol, d_mout;
   DevBuf<uint8_t> d_mwm;
-  std::vector<hipEvent_t> more_ev;
+  std::vector<DevEvent> more_ev;
   int more_ev_used = 0;
   DevBuf<double> d_qxyz;                // new points as uploaded (dense xyz)
   DevBuf<uint8_t> d_qmark;              // orphan marks (points of valid new tets), uploaded when needed
@@ -150,8 +145,7 @@ struct pmx_ctx {
   DevBuf<char> d_sqtmp;
   unsigned seq_stats[4] = {0, 0, 0, 0};   // surface replays / sequence, volume replays / sequence
   int64_t seq_stats_n = -1;             // -1: the last step was not sequential
-  int *d_tgrid = nullptr;
-  size_t d_tgrid_cap = 0;
+  DevBuf<int> d_tgrid;
   GridDesc tgd{};
   int64_t tcells = 0;
 
@@ -183,7 +177,7 @@ struct pmx_ctx {
   DevBuf<unsigned> d_gflag;
   DevBuf<char> d_gtmp;
   DevBuf<double> d_gfw;
-  std::vector<hipEvent_t> graph_ev;
+  DevEvent graph_ev[5];
   int graph_ev_n = 0;
   // Partition contiguity (pmx_contiguity / pmx_fix_contiguity, pmx_contig.hip),
   // ne + 1 words each: parents (labels once converged), marks, the replay's
@@ -195,7 +189,7 @@ struct pmx_ctx {
   DevBuf<int4> d_ctab, d_crec;
   DevBuf<int2> d_crecol;
   DevBuf<unsigned> d_cctl;
-  hipEvent_t contig_ev[2] = {};
+  DevEvent contig_ev[2];
   double contig_label_ms = -1.0, contig_replay_ms = -1.0;
   // Group split (pmx_split_groups / pmx_split_fetch, pmx_split.hip): the plan
   // with its device buffers, valid until the next
@@ -226,14 +220,14 @@ struct pmx_ctx {
   // from the new tets on the `topo` stream while the current step runs
   bool residency = false;
   hipStream_t topo = nullptr;
-  hipEvent_t ev_topo = nullptr;
+  DevEvent ev_topo;
   bool next_topo = false;               // d_tets_next / d_tets_s_next are being built
   DevBuf<TetRec> d_tets_next;
   DevBuf<WRec> d_wrec_next;
   DevBuf<int4> d_tets_s_next;
   // [2] / [3]: tets of d_wrec / d_wrec_next with a far neighbour field (pmx_wrec.h), [4]: bad fans,
   // [5]: entries of the vertex-owner hint sample
-  unsigned *h_nbad = nullptr;           // pinned [2]: non-manifold faces of that build, [1] of a background upload's
+  PinBuf<unsigned> h_nbad;              // pinned [2]: non-manifold faces of that build, [1] of a background upload's
   DevBuf<double> d_nqual;
   bool have_qtag = false;               // raw tags of the new points
   DevBuf<uint16_t> d_qtag;
@@ -243,9 +237,9 @@ struct pmx_ctx {
   // their DMA on `up` overlaps the step and the results' download (the step
   // itself never reads them); consumers wait for ev_tets (ensure_tets)
   hipStream_t up = nullptr;
-  hipEvent_t ev_tets = nullptr;
-  char *h_tets = nullptr;               // pinned copy of the current new tets (int4, 0 = deleted);
-  size_t h_tets_cap = 0;                // not the shared arena: it outlives the step (qualities' validity)
+  DevEvent ev_tets;
+  PinBuf<char> h_tets;                  // pinned copy of the current new tets (int4, 0 = deleted); not the
+                                        // shared arena: it outlives the step (qualities' validity)
   bool tets_pending = false;            // view kept, not packed yet
   bool view_tets = false;               // the points view carried new tets (orphans exist by definition)
   bool tets_inflight = false;           // DMA issued on `up`, ev_tets recorded
@@ -256,19 +250,18 @@ struct pmx_ctx {
   // PMX_RUN_EAGER_DOWNLOAD: the last step's fields (n * S doubles) and write
   // masks (n bytes) copied into h_out as soon as the step ends, in eager_nch
   // chunks (ev_eg); 0 = no such copy, or the results changed since
-  char *h_out = nullptr;
-  size_t h_out_cap = 0;
+  PinBuf<char> h_out;
   int eager_nch = 0;
-  hipEvent_t ev_eg[4] = {};
+  DevEvent ev_eg[4];
   DevBuf<double> d_gather;              // all-gathered partials
 
   // timing
   double topo_ms = 0.0;                 // device time of the last topology build
-  std::vector<hipEvent_t> events;
+  std::vector<DevEvent> events;
   int ev_used = 0;
 
-  hipEvent_t *next_event_slot();
-  void free_all();
+  ~pmx_ctx();                           // the split plan (pmx_capi.hip); the members release themselves
+  DevEvent *next_event_slot();          // nullptr + err on failure
   bool order_hint_samples(int64_t ne, int64_t nverts, hipStream_t s);
   // PMX_RUN_FRESH_BACKGROUND: the per-background device passes of an upload
   // (face matching + records when the device built the adjacency, compact
@@ -306,21 +299,7 @@ struct pmx_ctx {
   bool check_device_errors();
 };
 
-// grow-only device buffer (contents not kept); false + ctx->err on failure
-template <class T> inline bool pmx_dgrow(pmx_ctx *ctx, DevBuf<T> &b, size_t n) {
-  if (n <= b.cap && b.p) return true;
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-  const hipError_t e = hipMalloc((void **)&b.p, std::max<size_t>(n, 1) * sizeof(T));
-  if (e != hipSuccess) {
-    ctx->err = std::string("hipMalloc: ") + hipGetErrorString(e);
-    b.p = nullptr;
-    return false;
-  }
-  b.cap = n;
-  return true;
-}
+inline void pmx_set_error(pmx_ctx *ctx, std::string msg) { ctx->err = std::move(msg); }
 // the context's pinned staging arena, at least `bytes` (pmx_capi.hip)
 char *pmx_hstage(pmx_ctx *ctx, size_t bytes);
 // qualities dev[0..ne] (stream order) into the caller's array: stride 8

@@ -134,13 +134,7 @@ static void launch_more_bdy(const MoreArgs &a, int64_t nlist_ub, hipStream_t s) 
   hipLaunchKernelGGL(k_more_bdy, dim3((unsigned)nb), dim3(256), 0, s, a);
 }
 
-static bool mok(pmx_ctx *c, hipError_t e, const char *what) {
-  if (e == hipSuccess) return true;
-  c->err = std::string("pmx_interp_more: ") + what + ": " + hipGetErrorString(e);
-  return false;
-}
-#define MCK(x) do { if (!mok(ctx, (x), #x)) return 0; } while (0)
-static size_t mal256(size_t b) { return (b + 255) & ~(size_t)255; }
+#define CK(x) PMX_CK(C, x)
 
 double pmx_more_kernel_ms(pmx_ctx *ctx) {
   if (ctx->more_ev_used == 0) return -1.0;
@@ -179,21 +173,20 @@ extern "C" int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_s
     return 0;
   }
   hipSetDevice(ctx->device);
+  const pmx_call C{ctx, "pmx_interp_more", ctx->stream};
   ctx->more_ev_used = 0;
   // the orphans' rows first, as every consumer of the step's results
   if (!ctx->fix_orphans()) return 0;
   const int64_t n = ctx->nq, np = ctx->np;
   if (n == 0) {
-    MCK(hipStreamSynchronize(ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
     return ctx->check_device_errors() ? 1 : 0;
   }
   hipStream_t s = ctx->stream;
   const int nbatch = (nsol + PMX_MAX_SOLS - 1) / PMX_MAX_SOLS;
-  while (ctx->more_ev.size() < 2 * (size_t)nbatch) {
-    hipEvent_t e;
-    MCK(hipEventCreate(&e));
-    ctx->more_ev.push_back(e);
-  }
+  if (ctx->more_ev.size() < 2 * (size_t)nbatch) ctx->more_ev.resize(2 * (size_t)nbatch);
+  for (auto &e : ctx->more_ev)
+    if (!e.create()) return C.fail("event");
   for (int b = 0; b < nbatch; b++) {
     const int k0 = b * PMX_MAX_SOLS, nb = std::min(PMX_MAX_SOLS, nsol - k0);
     SolDesc sd{};
@@ -212,8 +205,8 @@ extern "C" int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_s
       return 0;
     // pinned arena: packed background rows | output rows | write masks (handed
     // out once the stream has drained: the previous batch is done with it)
-    const size_t o_in = 0, o_out = o_in + mal256(in_n * sizeof(double)),
-                 o_wm = o_out + mal256(out_n * sizeof(double)), total = o_wm + mal256((size_t)n);
+    const size_t o_in = 0, o_out = o_in + pmx_call::al256(in_n * sizeof(double)),
+                 o_wm = o_out + pmx_call::al256(out_n * sizeof(double)), total = o_wm + pmx_call::al256((size_t)n);
     char *stg = pmx_hstage(ctx, total);
     if (!stg) return 0;
     double *hs = (double *)(stg + o_in);
@@ -230,14 +223,14 @@ extern "C" int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_s
         }
       }
     });
-    MCK(hipMemcpyAsync(ctx->d_msol.p, hs, in_n * sizeof(double), hipMemcpyHostToDevice, s));
-    MCK(hipMemsetAsync(ctx->d_mwm.p, 0, (size_t)n, s));
+    CK(hipMemcpyAsync(ctx->d_msol.p, hs, in_n * sizeof(double), hipMemcpyHostToDevice, s));
+    CK(hipMemsetAsync(ctx->d_mwm.p, 0, (size_t)n, s));
     MoreArgs A{};
     A.xyz = ctx->d_xyz.p; A.tets = ctx->d_tets.p; A.tris = ctx->d_tris.p; A.ne = ctx->ne; A.nt = ctx->nt;
     A.sol = ctx->d_msol.p; A.sd = sd; A.q = ctx->d_qxyz.p; A.kind = ctx->d_kind.p;
     A.elem = ctx->d_elem.p; A.status = ctx->d_status.p; A.bphi = ctx->d_bphi.p;
     A.out = ctx->d_mout.p; A.wmask = ctx->d_mwm.p;
-    MCK(hipEventRecord(ctx->more_ev[2 * (size_t)b], s));
+    CK(hipEventRecord(ctx->more_ev[2 * (size_t)b], s));
     if (ctx->nq_vol_ub > 0) {
       A.list = ctx->d_vollist.p; A.nlist_dev = ctx->d_nsel.p;
       launch_more_vol(A, ctx->nq_vol_ub, s);
@@ -246,14 +239,14 @@ extern "C" int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_s
       A.list = ctx->d_bdylist.p; A.nlist_dev = ctx->d_nsel.p + 1;
       launch_more_bdy(A, ctx->nq_bdy_ub, s);
     }
-    MCK(hipEventRecord(ctx->more_ev[2 * (size_t)b + 1], s));
+    CK(hipEventRecord(ctx->more_ev[2 * (size_t)b + 1], s));
     ctx->more_ev_used = b + 1;
-    MCK(hipGetLastError());
+    CK(hipGetLastError());
     const double *ho = (const double *)(stg + o_out);
     const uint8_t *wm = (const uint8_t *)(stg + o_wm);
-    MCK(hipMemcpyAsync(stg + o_out, ctx->d_mout.p, out_n * sizeof(double), hipMemcpyDeviceToHost, s));
-    MCK(hipMemcpyAsync(stg + o_wm, ctx->d_mwm.p, (size_t)n, hipMemcpyDeviceToHost, s));
-    MCK(hipStreamSynchronize(s));
+    CK(hipMemcpyAsync(stg + o_out, ctx->d_mout.p, out_n * sizeof(double), hipMemcpyDeviceToHost, s));
+    CK(hipMemcpyAsync(stg + o_wm, ctx->d_mwm.p, (size_t)n, hipMemcpyDeviceToHost, s));
+    CK(hipStreamSynchronize(s));
     if (b == 0 && !ctx->check_device_errors()) return 0;   // the step's own error word
     // rows the reference leaves alone (no mask bit) are not written
     pmx_par_for(0, n, [&](int64_t i0, int64_t i1) {

@@ -430,47 +430,20 @@ struct pmx_split_plan {
   DevBuf<uint8_t> ff, fl, af;
   DevBuf<char> tmp;
   DevBuf<double> gx, gs;
-  hipEvent_t ev[2] = {};
+  DevEvent ev[2];
   int row(int r, int g) const { return gt[(size_t)r * (ngrp + 1) + g]; }
 };
 
 namespace {
 
-template <class T> void sp_free(DevBuf<T> &b) {
-  if (b.p) hipFree(b.p);
-  b.p = nullptr;
-  b.cap = 0;
-}
-
-struct Split {
-  pmx_ctx *ctx;
+struct Split : pmx_call {
   pmx_split_plan *pl;
-  hipStream_t s;
-  const char *who;
+  Split(pmx_ctx *c, const char *w) : pmx_call{c, w, c->stream}, pl(c->split) {}
 
-  bool fail(const std::string &what) { ctx->err = std::string(who) + ": " + what; return false; }
-  bool ok(hipError_t e, const char *what) { return e == hipSuccess || fail(what); }
-  static unsigned blocks(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
-  bool sync(const char *what) {
-    if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return fail(what);
-    return true;
-  }
+  // the stream synchronised and checked for launch errors
   bool read_ctl(unsigned *h) {
     return ok(hipMemcpyAsync(h, pl->ctl.p, sizeof(unsigned) * SC_NCTL, hipMemcpyDeviceToHost, s), "control words") &&
            sync("control words");
-  }
-  bool scratch(size_t bytes) { return pmx_dgrow(ctx, pl->tmp, bytes); }
-  template <class In> bool exsum(In in, int *out, int64_t n, const char *what) {
-    size_t b = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, b, in, out, (int)n, s);
-    return scratch(b) && ok(hipcub::DeviceScan::ExclusiveSum(pl->tmp.p, b, in, out, (int)n, s), what);
-  }
-  template <class K, class V>
-  bool sort(const K *kin, K *kout, const V *vin, V *vout, int64_t n, int bits, const char *what) {
-    size_t b = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, (int)n, 0, bits, s);
-    return scratch(b) && ok(hipcub::DeviceRadixSort::SortPairs(pl->tmp.p, b, kin, kout, vin, vout, (int)n, 0, bits, s),
-                            what);
   }
   bool up(DevBuf<int> &d, const int *h, int64_t n, const char *what) {
     return pmx_dgrow(ctx, d, (size_t)std::max<int64_t>(n, 1)) &&
@@ -514,8 +487,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
       !pmx_dgrow(ctx, P.epos, (size_t)nq + 1) || !pmx_dgrow(ctx, P.opos, (size_t)nq + 1) ||
       !pmx_dgrow(ctx, P.vcat, n1) || !pmx_dgrow(ctx, P.acat, n1))
     return false;
-  for (auto &e : P.ev)
-    if (!e && hipEventCreate(&e) != hipSuccess) return fail("event");
+  if (!pmx_create_events(P.ev)) return fail("event");
   if (!ok(hipEventRecord(P.ev[0], s), "event record")) return false;
   if (!ok(hipMemsetAsync(P.ctl.p, 0, sizeof(unsigned) * SC_NCTL, s), "memset") ||
       !ok(hipMemsetAsync(P.gtab.p, 0, sizeof(int) * (size_t)GT_ROWS * G1, s), "memset") ||
@@ -546,8 +518,8 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   }
 
   // tets: the stable order by part
-  if (!sort((const unsigned *)(P.part.p + 1), P.gcat.p, (const int *)P.iota.p, P.tcat.p, ne, bits_for((u64)ngrp),
-            "tet sort"))
+  if (!sort_pairs(P.tmp, (const unsigned *)(P.part.p + 1), P.gcat.p, (const int *)P.iota.p, P.tcat.p, ne,
+                  bits_for((u64)ngrp), "tet sort"))
     return false;
   int *gt = P.gtab.p;
   hipLaunchKernelGGL(k_sp_toff, dim3(blocks(G1)), dim3(256), 0, s, (const unsigned *)P.gcat.p, ne, ngrp, gt);
@@ -569,13 +541,9 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
     return false;
   hipLaunchKernelGGL(k_sp_first, dim3(blocks(ne)), dim3(256), 0, s, tets, (const int *)P.tcat.p, ne, P.first.p);
   {
-    size_t b = 0;
     hipcub::CountingInputIterator<unsigned> it(0u);
     const SideSel sel{recs, P.tcat.p, P.gcat.p, P.first.p};
-    hipcub::DeviceSelect::If(nullptr, b, it, P.side.p, P.ctl.p + SC_NSEL, (int)nq, sel, s);
-    if (!scratch(b) ||
-        !ok(hipcub::DeviceSelect::If(P.tmp.p, b, it, P.side.p, P.ctl.p + SC_NSEL, (int)nq, sel, s), "side select"))
-      return false;
+    if (!select_if(P.tmp, it, P.side.p, P.ctl.p + SC_NSEL, nq, sel, "side select")) return false;
   }
   if (!read_ctl(h)) return false;
   const int64_t nside = h[SC_NSEL];
@@ -586,8 +554,8 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   if (nside > 0) {
     hipLaunchKernelGGL(k_sp_sidekey, dim3(blocks(nside)), dim3(256), 0, s, (const unsigned *)P.side.p, nside, tets,
                        (const int *)P.tcat.p, (const unsigned *)P.gcat.p, P.skey.p);
-    if (!sort((const u64 *)P.skey.p, P.skey2.p, (const unsigned *)P.side.p, P.sval.p, nside,
-              32 + bits_for((u64)ngrp), "side sort"))
+    if (!sort_pairs(P.tmp, (const u64 *)P.skey.p, P.skey2.p, (const unsigned *)P.side.p, P.sval.p, nside,
+                    32 + bits_for((u64)ngrp), "side sort"))
       return false;
     hipLaunchKernelGGL(k_sp_flag_side, dim3(blocks(nside)), dim3(256), 0, s, (const u64 *)P.skey2.p,
                        (const unsigned *)P.sval.p, nside, P.ff.p);
@@ -595,7 +563,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   hipLaunchKernelGGL(k_sp_flag_first, dim3(blocks(np)), dim3(256), 0, s, (const unsigned *)P.first.p, np, P.ff.p);
   {
     hipcub::TransformInputIterator<int, U8Bit, const uint8_t *> in((const uint8_t *)P.ff.p, U8Bit{0});
-    if (!exsum(in, P.rank.p, nq + 1, "point scan")) return false;
+    if (!exclusive_sum(P.tmp, in, P.rank.p, nq + 1, "point scan")) return false;
   }
   hipLaunchKernelGGL(k_sp_gtab, dim3(blocks(G1)), dim3(256), 0, s, (const int *)P.rank.p, (const int *)gt, 4, ngrp,
                      gt + GT_P * G1);
@@ -628,7 +596,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   {
     hipcub::TransformInputIterator<int, U8Bit, const uint8_t *> e((const uint8_t *)P.fl.p, U8Bit{0});
     hipcub::TransformInputIterator<int, U8Bit, const uint8_t *> o((const uint8_t *)P.fl.p, U8Bit{1});
-    if (!exsum(e, P.epos.p, nq + 1, "face scan") || !exsum(o, P.opos.p, nq + 1, "owner scan")) return false;
+    if (!exclusive_sum(P.tmp, e, P.epos.p, nq + 1, "face scan") || !exclusive_sum(P.tmp, o, P.opos.p, nq + 1, "owner scan")) return false;
   }
   hipLaunchKernelGGL(k_sp_gtab, dim3(blocks(G1)), dim3(256), 0, s, (const int *)P.epos.p, (const int *)gt, 4, ngrp,
                      gt + GT_F * G1);
@@ -641,15 +609,10 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
                      (const unsigned *)P.ckey.p, P.af.p);
   {
     hipcub::TransformInputIterator<int, U8Bit, const uint8_t *> in((const uint8_t *)P.af.p, U8Bit{0});
-    if (!exsum(in, P.apos.p, P.NP + 1, "node scan")) return false;
-    size_t b = 0;
+    if (!exclusive_sum(P.tmp, in, P.apos.p, P.NP + 1, "node scan")) return false;
     hipcub::CountingInputIterator<int> it(0);
     hipcub::TransformInputIterator<int, U8Bit, const uint8_t *> fl((const uint8_t *)P.af.p, U8Bit{1});
-    hipcub::DeviceSelect::Flagged(nullptr, b, it, fl, P.clist.p, P.ctl.p + SC_NSEL, (int)P.NP, s);
-    if (!scratch(b) ||
-        !ok(hipcub::DeviceSelect::Flagged(P.tmp.p, b, it, fl, P.clist.p, P.ctl.p + SC_NSEL, (int)P.NP, s),
-            "node select"))
-      return false;
+    if (!select_flagged(P.tmp, it, fl, P.clist.p, P.ctl.p + SC_NSEL, P.NP, "node select")) return false;
   }
   if (!read_ctl(h)) return false;
   if (h[SC_LOOKUP]) return fail("inconsistent tet records (a vertex without a number, or a one-sided adjacency)");
@@ -658,8 +621,8 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   if (nC > 0) {
     hipLaunchKernelGGL(k_sp_ckey, dim3(blocks(nC)), dim3(256), 0, s, (const int *)P.clist.p, nC,
                        (const int *)P.pgrp.p, (const unsigned *)P.ckey.p, P.ckey64.p);
-    if (!sort((const u64 *)P.ckey64.p, P.ckey64b.p, (const int *)P.clist.p, P.cval.p, nC, 32 + bits_for((u64)ngrp),
-              "node sort"))
+    if (!sort_pairs(P.tmp, (const u64 *)P.ckey64.p, P.ckey64b.p, (const int *)P.clist.p, P.cval.p, nC,
+                    32 + bits_for((u64)ngrp), "node sort"))
       return false;
   }
   hipLaunchKernelGGL(k_sp_ntab, dim3(blocks(G1)), dim3(256), 0, s, (const int *)P.apos.p, (const u64 *)P.ckey64b.p,
@@ -695,21 +658,10 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
 }  // namespace
 
 void pmx_split_free(pmx_ctx *ctx) {
-  pmx_split_plan *P = ctx->split;
+  pmx_split_plan *P = ctx->split;      // its members release themselves
   ctx->split = nullptr;
   ctx->split_valid = false;
   ctx->split_plan_ms = ctx->split_fetch_ms = -1.0;
-  if (!P) return;
-  sp_free(P->part); sp_free(P->iota); sp_free(P->tcat); sp_free(P->tnew); sp_free(P->rank); sp_free(P->pcat);
-  sp_free(P->pgrp); sp_free(P->epos); sp_free(P->opos); sp_free(P->apos); sp_free(P->f1);
-  sp_free(P->f2); sp_free(P->n1); sp_free(P->n2); sp_free(P->gtab); sp_free(P->fold); sp_free(P->inidx);
-  sp_free(P->newval); sp_free(P->mincut); sp_free(P->clist); sp_free(P->cval); sp_free(P->in_f1); sp_free(P->in_f2);
-  sp_free(P->in_n1); sp_free(P->in_n2); sp_free(P->vcat); sp_free(P->acat); sp_free(P->gcat); sp_free(P->first);
-  sp_free(P->ckey); sp_free(P->side); sp_free(P->sval); sp_free(P->ctl); sp_free(P->skey); sp_free(P->skey2);
-  sp_free(P->ckey64); sp_free(P->ckey64b); sp_free(P->ff); sp_free(P->fl); sp_free(P->af); sp_free(P->tmp);
-  sp_free(P->gx); sp_free(P->gs);
-  for (auto &e : P->ev)
-    if (e) hipEventDestroy(e);
   delete P;
 }
 
@@ -724,7 +676,7 @@ int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_
   ctx->split_valid = false;
   ctx->split_plan_ms = ctx->split_fetch_ms = -1.0;
   if (!ctx->split) ctx->split = new pmx_split_plan();
-  Split S{ctx, ctx->split, ctx->stream, "pmx_split_groups"};
+  Split S{ctx, "pmx_split_groups"};
   if (!ctx->have_bg) { S.fail("upload a group first"); return 0; }
   const int64_t ne = ctx->ne, np = ctx->np;
   if (4 * ne >= (1LL << 31)) { S.fail("4 ne >= 2^31 (32-bit indices)"); return 0; }
@@ -777,7 +729,7 @@ int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_
 int pmx_split_fetch(pmx_ctx *ctx, int32_t g, const pmx_split_out *out) {
   if (!ctx) return 0;
   hipSetDevice(ctx->device);
-  Split S{ctx, ctx->split, ctx->stream, "pmx_split_fetch"};
+  Split S{ctx, "pmx_split_fetch"};
   if (!ctx->split || !ctx->split_valid) {
     S.fail("no plan: call pmx_split_groups (a background upload or promotion drops the plan)");
     return 0;

@@ -1896,40 +1896,36 @@ int pmx_metis_graph(pmx_ctx *ctx, int metRidTyp, int32_t *xadj, int32_t *adjncy,
   if (!xadj || !nadjncy || cap < 0) { ctx->err = std::string(who) + ": xadj / nadjncy are NULL or cap < 0"; return 0; }
   const int64_t ne = ctx->ne;
   hipStream_t s = ctx->stream;
-  auto fail = [&](const char *what) { ctx->err = std::string(who) + ": " + what; return 0; };
-  while (ctx->graph_ev.size() < 5) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return fail("event");
-    ctx->graph_ev.push_back(e);
-  }
+  const pmx_call C{ctx, who, s};
+  if (!pmx_create_events(ctx->graph_ev)) return C.fail("event");
   ctx->graph_ev_n = 0;
   size_t tb = 0;
   if (hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const int *)nullptr, (int *)nullptr, (int)(ne + 1), s) !=
       hipSuccess)
-    return fail("scan size");
+    return C.fail("scan size");
   if (!pmx_dgrow(ctx, ctx->d_gdeg, (size_t)(ne + 1)) || !pmx_dgrow(ctx, ctx->d_gxadj, (size_t)(ne + 1)) ||
       !pmx_dgrow(ctx, ctx->d_gflag, 1) || !pmx_dgrow(ctx, ctx->d_gtmp, tb))
     return 0;
-  const unsigned nbc = (unsigned)((ne + 1 + 255) / 256), nbf = (unsigned)std::max<int64_t>((ne + 255) / 256, 1);
-  if (hipMemsetAsync(ctx->d_gflag.p, 0, sizeof(unsigned), s) != hipSuccess) return fail("memset");
-  if (hipEventRecord(ctx->graph_ev[0], s) != hipSuccess) return fail("event record");
+  const unsigned nbc = (unsigned)((ne + 1 + 255) / 256), nbf = pmx_call::blocks(ne);
+  if (hipMemsetAsync(ctx->d_gflag.p, 0, sizeof(unsigned), s) != hipSuccess) return C.fail("memset");
+  if (hipEventRecord(ctx->graph_ev[0], s) != hipSuccess) return C.fail("event record");
   hipLaunchKernelGGL(k_graph_count, dim3(nbc), dim3(256), 0, s, (const TetRec *)ctx->d_tets.p, ne, ctx->d_gdeg.p,
                      ctx->d_gflag.p);
-  if (hipEventRecord(ctx->graph_ev[1], s) != hipSuccess) return fail("event record");
+  if (hipEventRecord(ctx->graph_ev[1], s) != hipSuccess) return C.fail("event record");
   if (hipcub::DeviceScan::InclusiveSum(ctx->d_gtmp.p, tb, (const int *)ctx->d_gdeg.p, ctx->d_gxadj.p, (int)(ne + 1),
                                        s) != hipSuccess)
-    return fail("scan");
-  if (hipEventRecord(ctx->graph_ev[2], s) != hipSuccess) return fail("event record");
-  if (hipGetLastError() != hipSuccess) return fail("count launch");
+    return C.fail("scan");
+  if (hipEventRecord(ctx->graph_ev[2], s) != hipSuccess) return C.fail("event record");
+  if (hipGetLastError() != hipSuccess) return C.fail("count launch");
   // the host needs nadjncy (and the flag) before it can size anything
   int tot = 0;
   unsigned flag = 0;
   if (hipMemcpyAsync(&tot, ctx->d_gxadj.p + ne, sizeof tot, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipMemcpyAsync(&flag, ctx->d_gflag.p, sizeof flag, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return fail("count download");
+    return C.fail("count download");
   ctx->graph_ev_n = 3;
-  if (flag) return fail("a deleted tet (v[0] <= 0): the reference wants a packed mesh");
+  if (flag) return C.fail("a deleted tet (v[0] <= 0): the reference wants a packed mesh");
   *nadjncy = tot;
   if (adjncy && tot > cap) {
     ctx->err = std::string(who) + ": adjncy holds " + std::to_string(cap) + " entries, nadjncy = " +
@@ -1947,11 +1943,11 @@ int pmx_metis_graph(pmx_ctx *ctx, int metRidTyp, int32_t *xadj, int32_t *adjncy,
       else if (A.msize == 6) kern = k_graph_fill<true, false, true, true>;
       else kern = k_graph_fill<false, false, true, true>;
     }
-    if (hipEventRecord(ctx->graph_ev[3], s) != hipSuccess) return fail("event record");
+    if (hipEventRecord(ctx->graph_ev[3], s) != hipSuccess) return C.fail("event record");
     hipLaunchKernelGGL(kern, dim3(nbf), dim3(256), 0, s, A, (const int *)ctx->d_gxadj.p, ctx->d_gadj.p,
                        adjwgt ? ctx->d_gwgt.p : (int *)nullptr);
-    if (hipEventRecord(ctx->graph_ev[4], s) != hipSuccess) return fail("event record");
-    if (hipGetLastError() != hipSuccess) return fail("fill launch");
+    if (hipEventRecord(ctx->graph_ev[4], s) != hipSuccess) return C.fail("event record");
+    if (hipGetLastError() != hipSuccess) return C.fail("fill launch");
   }
   if (hipMemcpyAsync(xadj, ctx->d_gxadj.p, sizeof(int32_t) * (size_t)(ne + 1), hipMemcpyDeviceToHost, s) !=
           hipSuccess ||
@@ -1962,7 +1958,7 @@ int pmx_metis_graph(pmx_ctx *ctx, int metRidTyp, int32_t *xadj, int32_t *adjncy,
        hipMemcpyAsync(adjwgt, ctx->d_gwgt.p, sizeof(int32_t) * (size_t)tot, hipMemcpyDeviceToHost, s) !=
            hipSuccess) ||
       hipStreamSynchronize(s) != hipSuccess)
-    return fail("download");
+    return C.fail("download");
   if (adjncy && tot > 0) ctx->graph_ev_n = 5;
   return 1;
 }
@@ -1974,8 +1970,8 @@ int pmx_face_weights(pmx_ctx *ctx, int metRidTyp, int64_t n, const int *face, do
   StatArgs A;
   bool surf = false;
   if (!graph_args(ctx, who, metRidTyp, A, surf)) return 0;
-  auto fail = [&](const char *what) { ctx->err = std::string(who) + ": " + what; return 0; };
-  if (n < 0 || (n > 0 && (!face || !wgt))) return fail("bad face list");
+  const pmx_call C{ctx, who, ctx->stream};
+  if (n < 0 || (n > 0 && (!face || !wgt))) return C.fail("bad face list");
   if (n == 0) return 1;
   for (int64_t i = 0; i < n; i++)
     if (face[i] < 12 || face[i] / 12 > ctx->ne) {
@@ -1983,13 +1979,13 @@ int pmx_face_weights(pmx_ctx *ctx, int metRidTyp, int64_t n, const int *face, do
                  " is outside 12 .. 12 ne + 11";
       return 0;
     }
-  hipStream_t s = ctx->stream;
+  hipStream_t s = C.s;
   if (!pmx_dgrow(ctx, ctx->d_gface, (size_t)n) || !pmx_dgrow(ctx, ctx->d_gfw, (size_t)n) ||
       !pmx_dgrow(ctx, ctx->d_gflag, 1))
     return 0;
   if (hipMemsetAsync(ctx->d_gflag.p, 0, sizeof(unsigned), s) != hipSuccess ||
       hipMemcpyAsync(ctx->d_gface.p, face, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s) != hipSuccess)
-    return fail("upload");
+    return C.fail("upload");
   using KW = void (*)(StatArgs, const int *, int64_t, double *, unsigned *);
   KW kern = k_face_weights<false, false, false>;
   if (A.msize != 0) {
@@ -1999,14 +1995,14 @@ int pmx_face_weights(pmx_ctx *ctx, int metRidTyp, int64_t n, const int *face, do
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A, (const int *)ctx->d_gface.p, n,
                      ctx->d_gfw.p, ctx->d_gflag.p);
-  if (hipGetLastError() != hipSuccess) return fail("launch");
+  if (hipGetLastError() != hipSuccess) return C.fail("launch");
   unsigned flag = 0;
   if (hipMemcpyAsync(&flag, ctx->d_gflag.p, sizeof flag, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return fail("flag download");
-  if (flag) return fail("a listed face belongs to a deleted tet");
+    return C.fail("flag download");
+  if (flag) return C.fail("a listed face belongs to a deleted tet");
   if (hipMemcpy(wgt, ctx->d_gfw.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail("download");
+    return C.fail("download");
   return 1;
 }
 

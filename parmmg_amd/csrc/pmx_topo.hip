@@ -255,33 +255,12 @@ __global__ __launch_bounds__(256) void k_bucket_of(const unsigned *__restrict__ 
 
 namespace {
 
-struct Scratch {
-  std::vector<void *> p;
-  ~Scratch() {
-    for (void *q : p) hipFree(q);
-  }
-  template <class T> T *get(size_t n) {
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-    p.push_back(q);
-    return (T *)q;
-  }
-};
-
-unsigned nblk(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
-
-// exclusive scan of n counts into off[0..n] (off[n] = total)
-bool scan_counts(const unsigned *cnt, unsigned *off, int64_t n, hipStream_t s, Scratch &sc) {
-  size_t bytes = 0;
-  hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, off, (int)(n + 1), s);
-  void *tmp = sc.get<char>(bytes);
-  if (!tmp) return false;
-  return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, cnt, off, (int)(n + 1), s) == hipSuccess;
-}
+// call-local device memory of n elements (released when the call returns);
+// nullptr on failure
+template <class T> T *local(pmx_ctx *ctx, DevBuf<T> &b, size_t n) { return pmx_dgrow(ctx, b, n) ? b.p : nullptr; }
 
 // strided host connectivity -> device int4 stream (1-based, slot 0 zero)
-int4 *upload_tets(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v, int64_t stride,
-                  Scratch &sc) {
+int4 *upload_tets(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v, int64_t stride, DevBuf<int4> &buf) {
   std::vector<int4> h((size_t)(ne + 1));
   h[0] = make_int4(0, 0, 0, 0);
   const char *tc = (const char *)tetra_v;
@@ -295,7 +274,7 @@ int4 *upload_tets(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v, int6
       }
     h[(size_t)k] = make_int4(v[0], v[1], v[2], v[3]);
   }
-  int4 *d = sc.get<int4>(h.size());
+  int4 *d = local(ctx, buf, h.size());
   if (!d) return nullptr;
   if (hipMemcpyAsync(d, h.data(), h.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream) !=
       hipSuccess)
@@ -304,31 +283,29 @@ int4 *upload_tets(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v, int6
   return d;
 }
 
-bool topo_fail(pmx_ctx *ctx, const char *what) {
-  ctx->err = what;
-  return false;
-}
-
 // device adjacency from the device connectivity stream
-bool build_adja_dev(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t np, int *dadja, Scratch &sc,
-                    unsigned *nbad_out) {
-  hipStream_t s = ctx->stream;
-  unsigned *cnt = sc.get<unsigned>((size_t)(np + 2));
-  unsigned *off = sc.get<unsigned>((size_t)(np + 2));
-  int4 *rec = sc.get<int4>((size_t)(4 * ne));
-  unsigned *nbad = sc.get<unsigned>(1);
-  if (!cnt || !off || !rec || !nbad) return topo_fail(ctx, "pmx_build_adja: hipMalloc");
+bool build_adja_dev(const pmx_call &C, const int4 *tv, int64_t ne, int64_t np, int *dadja, unsigned *nbad_out) {
+  pmx_ctx *ctx = C.ctx;
+  hipStream_t s = C.s;
+  DevBuf<unsigned> b_cnt, b_off, b_nbad;
+  DevBuf<int4> b_rec;
+  DevBuf<char> tmp;
+  unsigned *cnt = local(ctx, b_cnt, (size_t)(np + 2));
+  unsigned *off = local(ctx, b_off, (size_t)(np + 2));
+  int4 *rec = local(ctx, b_rec, (size_t)(4 * ne));
+  unsigned *nbad = local(ctx, b_nbad, 1);
+  if (!cnt || !off || !rec || !nbad) return C.fail("hipMalloc");
   hipMemsetAsync(cnt, 0, sizeof(unsigned) * (size_t)(np + 2), s);
   hipMemsetAsync(nbad, 0, sizeof(unsigned), s);
   hipMemsetAsync(dadja, 0, sizeof(int) * (size_t)(4 * ne + 5), s);
-  hipLaunchKernelGGL(k_face_count, dim3(nblk(ne)), dim3(256), 0, s, tv, ne, cnt);
-  if (!scan_counts(cnt, off, np + 1, s, sc)) return topo_fail(ctx, "pmx_build_adja: scan");
+  hipLaunchKernelGGL(k_face_count, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, ne, cnt);
+  if (!C.exclusive_sum(tmp, (const unsigned *)cnt, off, np + 2, "scan")) return C.fail("scan");
   hipMemcpyAsync(cnt, off, sizeof(unsigned) * (size_t)(np + 2), hipMemcpyDeviceToDevice, s);
-  hipLaunchKernelGGL(k_face_scatter, dim3(nblk(ne)), dim3(256), 0, s, tv, ne, cnt, rec);
+  hipLaunchKernelGGL(k_face_scatter, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, ne, cnt, rec);
   launch_face_match(rec, ne, np, off, dadja, nbad, s);
   if (hipMemcpyAsync(nbad_out, nbad, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return topo_fail(ctx, "pmx_build_adja: launch");
+    return C.fail("launch");
   return true;
 }
 
@@ -340,6 +317,7 @@ bool build_adja_dev(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t np, int *d
 // (promoted backgrounds: the new tets are already on the device)
 bool pmx_ctx_build_adja_device(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t np, int *dadja,
                                hipStream_t s, unsigned *h_nbad) {
+  const pmx_call C{ctx, "device adjacency", s};
   size_t bytes = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const unsigned *)nullptr, (unsigned *)nullptr,
                                    (int)(np + 2), s);
@@ -351,23 +329,23 @@ bool pmx_ctx_build_adja_device(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t
   bool okk = hipMemsetAsync(cnt, 0, sizeof(unsigned) * (size_t)(np + 2), s) == hipSuccess &&
              hipMemsetAsync(nbad, 0, sizeof(unsigned), s) == hipSuccess &&
              hipMemsetAsync(dadja, 0, sizeof(int) * (size_t)(4 * ne + 5), s) == hipSuccess;
-  if (!okk) return topo_fail(ctx, "device adjacency: memset");
-  hipLaunchKernelGGL(k_face_count, dim3(nblk(ne)), dim3(256), 0, s, tv, ne, cnt);
+  if (!okk) return C.fail("memset");
+  hipLaunchKernelGGL(k_face_count, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, ne, cnt);
   if (hipcub::DeviceScan::ExclusiveSum(ctx->d_ttmp.p, bytes, cnt, off, (int)(np + 2), s) != hipSuccess)
-    return topo_fail(ctx, "device adjacency: scan");
+    return C.fail("scan");
   hipMemcpyAsync(cnt, off, sizeof(unsigned) * (size_t)(np + 2), hipMemcpyDeviceToDevice, s);
-  hipLaunchKernelGGL(k_face_scatter, dim3(nblk(ne)), dim3(256), 0, s, tv, ne, cnt, ctx->d_trec.p);
+  hipLaunchKernelGGL(k_face_scatter, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, ne, cnt, ctx->d_trec.p);
   launch_face_match(ctx->d_trec.p, ne, np, off, dadja, nbad, s);
   if (h_nbad) {
     if (hipMemcpyAsync(h_nbad, nbad, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess)
-      return topo_fail(ctx, "device adjacency: launch");
+      return C.fail("launch");
     return true;
   }
   unsigned hb = 0;
   if (hipMemcpyAsync(&hb, nbad, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return topo_fail(ctx, "device adjacency: launch");
-  if (hb) return topo_fail(ctx, "device adjacency: non-manifold tet faces");
+    return C.fail("launch");
+  if (hb) return C.fail("non-manifold tet faces");
   return true;
 }
 
@@ -380,27 +358,27 @@ int pmx_build_adja(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v, int
     return 0;
   }
   hipSetDevice(ctx->device);
-  Scratch sc;
-  int4 *tv = upload_tets(ctx, ne, np, tetra_v, tetra_stride, sc);
+  const pmx_call C{ctx, "pmx_build_adja", ctx->stream};
+  DevBuf<int4> b_tv;
+  DevBuf<int> b_adja;
+  int4 *tv = upload_tets(ctx, ne, np, tetra_v, tetra_stride, b_tv);
   if (!tv) return 0;                             // pmx_last_error says why
-  int *dadja = sc.get<int>((size_t)(4 * ne + 5));
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
+  int *dadja = local(ctx, b_adja, (size_t)(4 * ne + 5));
+  DevEvent e0, e1;
+  e0.create();
+  e1.create();
   hipEventRecord(e0, ctx->stream);
   unsigned nbad = 0;
-  const bool ok = dadja && build_adja_dev(ctx, tv, ne, np, dadja, sc, &nbad);
+  const bool ok = dadja && build_adja_dev(C, tv, ne, np, dadja, &nbad);
   hipEventRecord(e1, ctx->stream);
   hipEventSynchronize(e1);
   float ms = 0.f;
   hipEventElapsedTime(&ms, e0, e1);
   ctx->topo_ms = ms;
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
   if (!ok) return 0;
   if (hipMemcpy(adja, dadja, sizeof(int) * (size_t)(4 * ne + 5), hipMemcpyDeviceToHost) != hipSuccess)
-    return topo_fail(ctx, "pmx_build_adja: download"), 0;
-  if (nbad) return topo_fail(ctx, "pmx_build_adja: non-manifold tet faces (left 0)"), 0;
+    return C.fail("download");
+  if (nbad) return C.fail("non-manifold tet faces (left 0)");
   return 1;
 }
 
@@ -412,45 +390,50 @@ int64_t pmx_build_bdry(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v,
   }
   hipSetDevice(ctx->device);
   hipStream_t s = ctx->stream;
-  Scratch sc;
-  int4 *tv = upload_tets(ctx, ne, np, tetra_v, tetra_stride, sc);
-  int *dadja = sc.get<int>((size_t)(4 * ne + 5));
-  unsigned *tcnt = sc.get<unsigned>((size_t)(ne + 1));
-  unsigned *tpos = sc.get<unsigned>((size_t)(ne + 1));
-  if (!tv || !dadja || !tcnt || !tpos) return topo_fail(ctx, "pmx_build_bdry: hipMalloc"), -1;
+  const pmx_call C{ctx, "pmx_build_bdry", s};
+  DevBuf<int4> b_tv;
+  DevBuf<int> b_adja, b_tria, b_bof, b_adjt;
+  DevBuf<unsigned> b_tcnt, b_tpos, b_cnt, b_off;
+  DevBuf<int2> b_rec;
+  DevBuf<char> tmp, tmp2;                        // one per scan: no free while the first is queued
+  int4 *tv = upload_tets(ctx, ne, np, tetra_v, tetra_stride, b_tv);
+  int *dadja = local(ctx, b_adja, (size_t)(4 * ne + 5));
+  unsigned *tcnt = local(ctx, b_tcnt, (size_t)(ne + 1));
+  unsigned *tpos = local(ctx, b_tpos, (size_t)(ne + 1));
+  if (!tv || !dadja || !tcnt || !tpos) return C.fail("hipMalloc"), -1;
   hipMemcpyAsync(dadja, adja, sizeof(int) * (size_t)(4 * ne + 5), hipMemcpyHostToDevice, s);
   hipMemsetAsync(tcnt, 0, sizeof(unsigned) * (size_t)(ne + 1), s);
-  hipEvent_t e0, e1;
-  hipEventCreate(&e0);
-  hipEventCreate(&e1);
+  DevEvent e0, e1;
+  e0.create();
+  e1.create();
   hipEventRecord(e0, s);
-  hipLaunchKernelGGL(k_bdry_count, dim3(nblk(ne)), dim3(256), 0, s, tv, dadja, ne, tcnt);
-  if (!scan_counts(tcnt, tpos, ne, s, sc)) return topo_fail(ctx, "pmx_build_bdry: scan"), -1;
+  hipLaunchKernelGGL(k_bdry_count, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, dadja, ne, tcnt);
+  if (!C.exclusive_sum(tmp, (const unsigned *)tcnt, tpos, ne + 1, "scan")) return C.fail("scan"), -1;
   unsigned nt_u = 0;
   hipMemcpyAsync(&nt_u, tpos + ne, sizeof(unsigned), hipMemcpyDeviceToHost, s);
   hipStreamSynchronize(s);
   const int64_t nt = nt_u;
-  if (nt > maxnt) return topo_fail(ctx, "pmx_build_bdry: more boundary faces than maxnt"), -1;
-  int *dtria = sc.get<int>((size_t)(3 * (nt + 1)));
-  if (!dtria) return topo_fail(ctx, "pmx_build_bdry: hipMalloc"), -1;
+  if (nt > maxnt) return C.fail("more boundary faces than maxnt"), -1;
+  int *dtria = local(ctx, b_tria, (size_t)(3 * (nt + 1)));
+  if (!dtria) return C.fail("hipMalloc"), -1;
   hipMemsetAsync(dtria, 0, sizeof(int) * 3, s);
-  hipLaunchKernelGGL(k_bdry_write, dim3(nblk(ne)), dim3(256), 0, s, tv, dadja, ne, tpos, dtria);
+  hipLaunchKernelGGL(k_bdry_write, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, dadja, ne, tpos, dtria);
   int *dadjt = nullptr;
   if (adjt && nt > 0) {
-    unsigned *cnt = sc.get<unsigned>((size_t)(np + 2));
-    unsigned *off = sc.get<unsigned>((size_t)(np + 2));
-    int2 *rec = sc.get<int2>((size_t)(3 * nt));
-    int *bof = sc.get<int>((size_t)(3 * nt));
-    dadjt = sc.get<int>((size_t)(3 * nt + 4));
-    if (!cnt || !off || !rec || !bof || !dadjt) return topo_fail(ctx, "pmx_build_bdry: hipMalloc"), -1;
+    unsigned *cnt = local(ctx, b_cnt, (size_t)(np + 2));
+    unsigned *off = local(ctx, b_off, (size_t)(np + 2));
+    int2 *rec = local(ctx, b_rec, (size_t)(3 * nt));
+    int *bof = local(ctx, b_bof, (size_t)(3 * nt));
+    dadjt = local(ctx, b_adjt, (size_t)(3 * nt + 4));
+    if (!cnt || !off || !rec || !bof || !dadjt) return C.fail("hipMalloc"), -1;
     hipMemsetAsync(cnt, 0, sizeof(unsigned) * (size_t)(np + 2), s);
     hipMemsetAsync(dadjt, 0, sizeof(int) * (size_t)(3 * nt + 4), s);
-    hipLaunchKernelGGL(k_edge_count, dim3(nblk(3 * nt)), dim3(256), 0, s, dtria, nt, cnt);
-    if (!scan_counts(cnt, off, np + 1, s, sc)) return topo_fail(ctx, "pmx_build_bdry: scan"), -1;
+    hipLaunchKernelGGL(k_edge_count, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, dtria, nt, cnt);
+    if (!C.exclusive_sum(tmp2, (const unsigned *)cnt, off, np + 2, "scan")) return C.fail("scan"), -1;
     hipMemcpyAsync(cnt, off, sizeof(unsigned) * (size_t)(np + 2), hipMemcpyDeviceToDevice, s);
-    hipLaunchKernelGGL(k_edge_scatter, dim3(nblk(3 * nt)), dim3(256), 0, s, dtria, nt, cnt, rec);
-    hipLaunchKernelGGL(k_bucket_of, dim3(nblk(np + 1)), dim3(256), 0, s, off, np + 1, bof);
-    hipLaunchKernelGGL(k_edge_match, dim3(nblk(3 * nt)), dim3(256), 0, s, rec, 3 * nt, off, bof,
+    hipLaunchKernelGGL(k_edge_scatter, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, dtria, nt, cnt, rec);
+    hipLaunchKernelGGL(k_bucket_of, dim3(pmx_call::blocks(np + 1)), dim3(256), 0, s, off, np + 1, bof);
+    hipLaunchKernelGGL(k_edge_match, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, rec, 3 * nt, off, bof,
                        dadjt);
   }
   hipEventRecord(e1, s);
@@ -458,14 +441,12 @@ int64_t pmx_build_bdry(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v,
   float ms = 0.f;
   hipEventElapsedTime(&ms, e0, e1);
   ctx->topo_ms = ms;
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  if (hipGetLastError() != hipSuccess) return topo_fail(ctx, "pmx_build_bdry: launch"), -1;
+  if (hipGetLastError() != hipSuccess) return C.fail("launch"), -1;
   if (hipMemcpy(tria, dtria, sizeof(int) * (size_t)(3 * (nt + 1)), hipMemcpyDeviceToHost) != hipSuccess)
-    return topo_fail(ctx, "pmx_build_bdry: download"), -1;
+    return C.fail("download"), -1;
   if (dadjt &&
       hipMemcpy(adjt, dadjt, sizeof(int) * (size_t)(3 * nt + 4), hipMemcpyDeviceToHost) != hipSuccess)
-    return topo_fail(ctx, "pmx_build_bdry: download"), -1;
+    return C.fail("download"), -1;
   return nt;
 }
 
