@@ -24,6 +24,9 @@
  *       (src/moveinterfaces_pmmg.c:377-611) -> pmx_fix_contiguity
  *   PMMG_split_eachGrp (src/grpsplit_pmmg.c:1267-1445)
  *                                          -> pmx_split_groups / pmx_split_fetch
+ *   PMMG_merge_grps (src/mergemesh_pmmg.c:967-1073)
+ *                                          -> pmx_merge_groups / pmx_merge_fetch /
+ *                                             pmx_merge_adopt
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -332,7 +335,10 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * the last pmx_contiguity or pmx_fix_contiguity, summed (-1 before the first
  * call or after a refusal).
  * which = 14 / 15: the last pmx_split_groups / the last pmx_split_fetch after
- * it (-1 before the first, after a refusal of the plan and after a release). */
+ * it (-1 before the first, after a refusal of the plan and after a release).
+ * which = 16 / 17 / 18: the last pmx_merge_groups / pmx_merge_fetch /
+ * pmx_merge_adopt (each -1 before its first call, after a refusal of the plan
+ * and after a release). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -731,6 +737,110 @@ typedef struct {
 int pmx_split_fetch(pmx_ctx *ctx, int32_t g, const pmx_split_out *out);
 /* Frees the plan's device memory (pmx_destroy does too). */
 int pmx_split_release(pmx_ctx *ctx);
+
+/* A rank's groups merged into one: PMMG_merge_grps (src/mergemesh_pmmg.c:
+ * 967-1073) for packed groups, the first step of PMMG_split_n2mGrps
+ * (src/grpsplit_pmmg.c:1736-1850) -- the merged points and tets in the
+ * reference's order, the face and node slots of the internal communicators and
+ * the merged communicators it rebuilds from the external ones (DESIGN.md
+ * section 4, "Group merge").  Not produced: xPoint / xTetra copies, ref, tag,
+ * qual (copy them through the maps), PMMG_updateTag.
+ *
+ * One group, in the vocabulary of pmx_split_out (a fetched group is a valid
+ * input): point_c / tetra_v through byte strides, entries 1..np / 1..ne, as
+ * pmx_mesh_view; sols: the call's nsol views, m holding (np+1)*size doubles;
+ * node2int_node_comm_index1/2 (nnode entries: the local point, the position)
+ * and face2int_face_comm_index1/2 (nface entries: 12*iel + 3*ifac + iploc,
+ * the position). */
+typedef struct {
+  int64_t             np, ne;
+  const double       *point_c;  int64_t point_stride;
+  const int          *tetra_v;  int64_t tetra_stride;
+  const pmx_sol_view *sols;
+  int64_t             nnode, nface;
+  const int          *node_index1, *node_index2, *face_index1, *face_index2;
+} pmx_merge_group;
+/* int_node_comm->nitem and int_face_comm->nitem on entry, and the rank's
+ * external communicators as two CSR lists: next_node / next_face
+ * communicators, node_off / face_off (next + 1 offsets, the first 0) into the
+ * concatenated int_comm_index values node_items / face_items.  next = 0 (the
+ * offsets and items may then be NULL) is the one-process case: both merged
+ * communicators come out empty. */
+typedef struct {
+  int64_t        int_node_nitem, int_face_nitem;
+  int32_t        next_node, next_face;
+  const int64_t *node_off, *face_off;
+  const int     *node_items, *face_items;
+} pmx_merge_comm;
+/* the merged group: points, tets, node2int_node_comm and face2int_face_comm
+ * entries (= the two nitem after the merge) */
+typedef struct { int64_t np, ne, nnode, nface; } pmx_merge_sizes;
+
+/* The plan: the ngrp >= 1 groups are packed from the host views, uploaded and
+ * merged on the device, where the result stays until pmx_merge_release, the
+ * next pmx_merge_groups or pmx_destroy.  It neither needs, reads nor disturbs
+ * an uploaded background; pmx_upload_background / pmx_promote_background do
+ * not drop it.  comm NULL: both nitem 0, no external communicator.
+ * Returns 0 (pmx_last_error), sizes untouched and no plan left: ngrp < 1; a
+ * NULL view; a deleted tet (v[0] <= 0); a vertex outside 1..np_g; nsol outside
+ * 0..PMX_MAX_SOLS, or a solution size that is not 1, 3 or 6 or differs between
+ * groups; a node entry's point outside 1..np_g or its position outside
+ * 0..int_node_nitem-1; a face entry outside 12..12*ne_g+11 or its position
+ * outside 0..int_face_nitem-1; an external item out of range, or naming a slot
+ * nothing filled (the reference asserts); a merged point that an external
+ * node communicator holds twice, the first time as its first appearance (the
+ * reference's poi_id_glo == nitem assert); the groups' points together, or the
+ * merged np, >= 2^31 - 1; 12*ne + 11 >= 2^31.
+ * pmx_kernel_ms(ctx, 16): the plan's device time (first to last device
+ * operation of the call, the uploads and the small downloads included);
+ * 17: the last pmx_merge_fetch; 18: the last pmx_merge_adopt; each -1 before
+ * its first call, after a refused plan and after a release. */
+int pmx_merge_groups(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_group *groups, int nsol,
+                     const pmx_merge_comm *comm, pmx_merge_sizes *sizes);
+
+/* The merged group's arrays, sized by the plan's sizes; every pointer may be
+ * NULL (not fetched):
+ *   tetra_v        4*(ne+1) ints, Mmg layout: rows 1..ne written
+ *   tet_group      ne ints: the group merged tet j came from, at j-1 (what
+ *                  PMMG_set_color_tetra leaves in mark)
+ *   tet_old        ne ints: its local id in that group
+ *   point_group    np ints: the group whose copy created merged point i, at i-1
+ *   point_old      np ints: that copy's local id
+ *   xyz            3*(np+1) doubles, rows 1..np written: the creating copy's
+ *   sols           nsol = 0 (none) or the plan's, of the plan's sizes: m holds
+ *                  (np+1)*size doubles, rows 1..np written
+ *   node_index1/2  nnode ints each: the merged point and its position
+ *   face_index1/2  nface ints each: 12*ie + 3*ifac + iploc and the position
+ *   ext_node_items / ext_face_items  the external communicators' rewritten
+ *                  int_comm_index, in the input's CSR layout
+ * Returns 0, the arrays untouched: no plan; solution views that do not match
+ * the plan's.  A device error during the copies may leave them partly written. */
+typedef struct {
+  int *tetra_v, *tet_group, *tet_old, *point_group, *point_old;
+  double *xyz;
+  int nsol;
+  const pmx_sol_view *sols;
+  int *node_index1, *node_index2, *face_index1, *face_index2, *ext_node_items, *ext_face_items;
+} pmx_merge_out;
+int pmx_merge_fetch(pmx_ctx *ctx, const pmx_merge_out *out);
+
+/* Group g's local-to-merged maps: point_new (np_g ints, local point k at k-1:
+ * meshJ->point[k].tmp) and tet_new (ne_g ints: tetra[k].flag); either may be
+ * NULL.  Returns 0, the arrays untouched: no plan; g outside 0..ngrp-1. */
+int pmx_merge_maps(pmx_ctx *ctx, int32_t g, int *point_new, int *tet_new);
+
+/* The merged group becomes the context's uploaded group without crossing
+ * PCIe: the context ends in the state pmx_upload_background of the fetched
+ * arrays with adja = NULL, nt = 0 and the same imet leaves (tet records by
+ * device face matching -- the reference's MMG3D_hashTetra after the merge,
+ * src/grpsplit_pmmg.c:1815-1821 --, xyz, the interleaved solutions, grids and
+ * hint samples; the same flags invalidated, a split plan included).  The
+ * merge plan survives and stays fetchable.  Returns 0: no plan; imet outside
+ * -1..nsol-1; 4*ne >= 2^31; non-manifold faces (the context then holds no
+ * background, as after a failed upload). */
+int pmx_merge_adopt(pmx_ctx *ctx, int imet);
+/* Frees the plan's device memory (pmx_destroy does too). */
+int pmx_merge_release(pmx_ctx *ctx);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

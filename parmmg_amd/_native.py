@@ -165,6 +165,33 @@ class SplitOut(C.Structure):
                [("xyz", dptr), ("nsol", C.c_int), ("sols", C.POINTER(SolView))]
 
 
+class MergeGroup(C.Structure):
+    """pmx_merge_group: one of the rank's groups."""
+    _fields_ = [("np", i64), ("ne", i64), ("point_c", dptr), ("point_stride", i64),
+                ("tetra_v", iptr), ("tetra_stride", i64), ("sols", C.POINTER(SolView)),
+                ("nnode", i64), ("nface", i64),
+                ("node_index1", iptr), ("node_index2", iptr), ("face_index1", iptr), ("face_index2", iptr)]
+
+
+class MergeComm(C.Structure):
+    """pmx_merge_comm: the internal communicators' nitem and the external ones (CSR)."""
+    _fields_ = [("int_node_nitem", i64), ("int_face_nitem", i64), ("next_node", C.c_int32), ("next_face", C.c_int32),
+                ("node_off", C.POINTER(i64)), ("face_off", C.POINTER(i64)), ("node_items", iptr), ("face_items", iptr)]
+
+
+class MergeSizes(C.Structure):
+    """pmx_merge_sizes."""
+    _fields_ = [(n, i64) for n in ("np", "ne", "nnode", "nface")]
+
+
+class MergeOut(C.Structure):
+    """pmx_merge_out: the merged group's arrays (NULL: not fetched)."""
+    _fields_ = [(n, iptr) for n in ("tetra_v", "tet_group", "tet_old", "point_group", "point_old")] + \
+               [("xyz", dptr), ("nsol", C.c_int), ("sols", C.POINTER(SolView))] + \
+               [(n, iptr) for n in ("node_index1", "node_index2", "face_index1", "face_index2", "ext_node_items",
+                                    "ext_face_items")]
+
+
 INQUA, OUTQUA, LESQUA = 0, 1, 2
 
 
@@ -231,6 +258,12 @@ SIGNATURES = {
                                    C.POINTER(i64), C.POINTER(i64)]),
     "pmx_split_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SplitOut)]),
     "pmx_split_release": (C.c_int, [C.c_void_p]),
+    "pmx_merge_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MergeGroup), C.c_int, C.POINTER(MergeComm),
+                                   C.POINTER(MergeSizes)]),
+    "pmx_merge_fetch": (C.c_int, [C.c_void_p, C.POINTER(MergeOut)]),
+    "pmx_merge_maps": (C.c_int, [C.c_void_p, C.c_int32, iptr, iptr]),
+    "pmx_merge_adopt": (C.c_int, [C.c_void_p, C.c_int]),
+    "pmx_merge_release": (C.c_int, [C.c_void_p]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

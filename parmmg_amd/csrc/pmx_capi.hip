@@ -1686,6 +1686,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && which >= 8 && which <= 11) return pmx_graph_kernel_ms(ctx, which);
   if (ctx && (which == 12 || which == 13)) return pmx_contig_kernel_ms(ctx, which);
   if (ctx && (which == 14 || which == 15)) return pmx_split_kernel_ms(ctx, which);
+  if (ctx && which >= 16 && which <= 18) return pmx_merge_kernel_ms(ctx, which);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
@@ -2014,5 +2015,59 @@ DevEvent *pmx_ctx::next_event_slot() {
   return r;
 }
 
-pmx_ctx::~pmx_ctx() { pmx_split_free(this); }
+pmx_ctx::~pmx_ctx() {
+  pmx_split_free(this);
+  pmx_merge_free(this);
+}
+
+// ---- a device-resident group as the background (pmx_merge_adopt) ----------------
+
+// pmx_upload_background's device-adjacency path with nt = 0, its host packing
+// and DMA replaced by device-to-device copies
+bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
+                         const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]) {
+  const pmx_call call{ctx, who, ctx->stream};
+  ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
+  ctx->have_pmap = false;
+  ctx->split_valid = false;
+  ctx->eager_nch = 0;
+  ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = false;
+  ctx->stat_np = -1;
+  if (np < 1 || ne < 1 || np >= (1LL << 31) - 1 || 4 * ne >= (1LL << 31)) return call.fail("mesh sizes out of range");
+  ctx->compact_recs = env_compact_records();
+  ctx->sample_mode = env_sample_mode();
+  ctx->bg_btv = false;
+  if (ctx->next_topo && !call.hip(hipStreamSynchronize(ctx->topo), "residency build")) return false;
+  const int S = sd.S;
+  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
+  const size_t hs_n = (size_t)(np + 1) * std::max(S, 1);
+  if (!pmx_dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) || !pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) ||
+      (ctx->compact_recs && !pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !pmx_dgrow(ctx, ctx->d_wfar, 8) ||
+      !pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) || !pmx_dgrow(ctx, ctx->d_sol, hs_n) ||
+      !pmx_dgrow(ctx, ctx->d_tris, 1) || !pmx_dgrow(ctx, ctx->d_trn, 1) ||
+      !pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) || !pmx_dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) ||
+      !pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)))
+    return false;
+  hipStream_t st = ctx->stream;
+  if (!call.hip(hipMemcpyAsync(ctx->d_xyz.p, xyz, (size_t)(np + 1) * 24, hipMemcpyDeviceToDevice, st), "points") ||
+      !call.hip(hipMemcpyAsync(ctx->d_btv.p, tv, (size_t)(ne + 1) * sizeof(int4), hipMemcpyDeviceToDevice, st), "tets") ||
+      !call.hip(S > 0 ? hipMemcpyAsync(ctx->d_sol.p, sol, hs_n * sizeof(double), hipMemcpyDeviceToDevice, st)
+                      : hipMemsetAsync(ctx->d_sol.p, 0, hs_n * sizeof(double), st), "solutions") ||
+      !call.hip(hipMemsetAsync(ctx->d_tris.p, 0, sizeof(TriRec), st), "trias"))
+    return false;
+  ctx->h_nbad.p[1] = ctx->h_nbad.p[2] = 0;
+  if (!pmx_ctx_build_adja_device(ctx, ctx->d_btv.p, ne, np, ctx->d_adja.p, st, ctx->h_nbad.p + 1)) return false;
+  launch_build_tetrec(ctx->d_btv.p, ctx->d_adja.p, ne, PMX_HINT_STRIDE, ctx->d_tets.p, ctx->d_tets_s.p, st);
+  if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, st);
+  if (!ctx->order_hint_samples(ne, np, st)) return false;
+  ctx->np = np; ctx->ne = ne; ctx->nt = 0; ctx->hausd = 0.0;
+  ctx->sd = sd;
+  if (!setup_grids(ctx, lo, hi, ne) || !ctx->check_fans(st)) return false;
+  if (!call.hip(hipGetLastError(), "launch") || !call.hip(hipStreamSynchronize(st), "sync")) return false;
+  if (ctx->h_nbad.p[1]) return call.fail("non-manifold tet faces");
+  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[5] : 0;
+  ctx->bg_btv = true;
+  ctx->have_bg = true;
+  return true;
+}
 

@@ -197,7 +197,13 @@ struct pmx_ctx {
   struct pmx_split_plan *split = nullptr;
   bool split_valid = false;
   double split_plan_ms = -1.0, split_fetch_ms = -1.0;
-  int64_t stat_np = -1;                 // node count of pmx_count_nodes (-1: np)
+  // Group merge (pmx_merge_groups / _fetch / _maps / _adopt, pmx_merge.hip):
+  // the plan with its device buffers, independent of the background (an
+  // upload or a promotion leaves it alone); device times of the last plan /
+  // fetch / adopt
+  struct pmx_merge_plan *merge = nullptr;
+  double merge_plan_ms = -1.0, merge_fetch_ms = -1.0, merge_adopt_ms = -1.0;
+  int64_t stat_np = -1;                // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
   DevBuf<double> d_pub;                 // public partial records of the host wrappers
@@ -332,5 +338,16 @@ double pmx_contig_kernel_ms(pmx_ctx *ctx, int which);
 // and its buffers freed (pmx_split.hip)
 double pmx_split_kernel_ms(pmx_ctx *ctx, int which);
 void pmx_split_free(pmx_ctx *ctx);
+// pmx_kernel_ms(ctx, 16 / 17 / 18): the last merge plan / fetch / adopt; the
+// plan and its buffers freed (pmx_merge.hip)
+double pmx_merge_kernel_ms(pmx_ctx *ctx, int which);
+void pmx_merge_free(pmx_ctx *ctx);
+// A group that is already on the device (connectivity tv: 1-based int4, slot 0
+// unused; xyz: 3 (np + 1) doubles; sol: (np + 1) max(S, 1) doubles, interleaved;
+// bounding box lo / hi) becomes the uploaded group, as pmx_upload_background
+// with adja = NULL and nt = 0 leaves it; the copies are device to device on
+// the context stream (pmx_capi.hip).  false + ctx->err, no background kept.
+bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
+                         const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]);
 // error of a call made without a context (pmx_last_error(NULL), per thread)
 void pmx_set_noctx_error(const char *msg);

@@ -18,6 +18,10 @@ Names and argument meaning follow the reference:
 * :meth:`Transfer.split_groups`, :meth:`Transfer.split_fetch`,
   :meth:`Transfer.split_release` -- the new groups of ``PMMG_split_eachGrp``
   (src/grpsplit_pmmg.c).
+* :meth:`Transfer.merge_groups`, :meth:`Transfer.merge_fetch`,
+  :meth:`Transfer.merge_maps`, :meth:`Transfer.merge_adopt`,
+  :meth:`Transfer.merge_release` -- ``PMMG_merge_grps``
+  (src/mergemesh_pmmg.c), the merged group kept on the device.
 
 Errors follow the reference's 1/0 convention at the C ABI and surface here as
 ``RuntimeError`` with ``pmx_last_error``.  Everything runs on the GPU; there is
@@ -670,6 +674,133 @@ class Transfer:
         """Free the plan's device memory (pmx_split_release)."""
         self._split_sizes = None
         self._chk(self.lib.pmx_split_release(self.ctx), "pmx_split_release")
+
+    # ---- group merge ----------------------------------------------------------
+    def _merge_views(self, groups: list[dict], comm: dict | None = None):
+        """The pmx_merge_group array, nsol, the pmx_merge_comm and the numpy
+        arrays they point into (kept alive by the caller), from the dicts
+        merge_groups takes."""
+        comm = comm or {}
+        ngrp = len(groups)
+        keep = []
+        i32 = lambda a: np.ascontiguousarray(a, np.int32)
+        gv = (N.MergeGroup * max(ngrp, 1))()
+        nsol = len(groups[0]["sols"]) if ngrp else 0
+        for g, d in enumerate(groups):
+            tv, xyz = i32(d["tetra_v"]), np.ascontiguousarray(d["xyz"], np.float64)
+            sols = [np.ascontiguousarray(s, np.float64) for s in d["sols"]]
+            if len(sols) != nsol:
+                raise ValueError("the groups differ in their number of solutions")
+            views = (N.SolView * max(nsol, 1))()
+            for i, a in enumerate(sols):
+                views[i].size = a.shape[1] if a.ndim == 2 else 1
+                views[i].m = _dp(a)
+            idx = {k: i32(d.get(k, np.zeros(0))) for k in ("node_index1", "node_index2", "face_index1", "face_index2")}
+            if len(idx["node_index1"]) != len(idx["node_index2"]) or len(idx["face_index1"]) != len(idx["face_index2"]):
+                raise ValueError("index1 and index2 of a communicator differ in length")
+            keep += [tv, xyz, sols, views, idx]
+            v = gv[g]
+            v.np, v.ne = xyz.shape[0] - 1, tv.shape[0] - 1
+            v.point_c, v.point_stride = _dp(xyz), 24
+            v.tetra_v, v.tetra_stride = _ip(tv), 16
+            v.sols = views
+            v.nnode, v.nface = len(idx["node_index1"]), len(idx["face_index1"])
+            for k, a in idx.items():
+                setattr(v, k, _ip(a) if a.size else None)
+        c = N.MergeComm()
+        c.int_node_nitem = int(comm.get("int_node_nitem", 0))
+        c.int_face_nitem = int(comm.get("int_face_nitem", 0))
+        ext = {}
+        for kind in ("node", "face"):
+            lists = [i32(a) for a in comm.get("ext_" + kind, [])]
+            off = np.zeros(len(lists) + 1, np.int64)
+            off[1:] = np.cumsum([len(a) for a in lists])
+            items = np.concatenate(lists) if lists else np.zeros(0, np.int32)
+            ext[kind] = (off, i32(items))
+            setattr(c, "next_" + kind, len(lists))
+            setattr(c, kind + "_off", off.ctypes.data_as(C.POINTER(N.i64)) if lists else None)
+            setattr(c, kind + "_items", _ip(ext[kind][1]) if items.size else None)
+        meta = {"sol_sizes": [int(v.size) for v in keep[3][:nsol]] if ngrp else [],
+                "nen": len(ext["node"][1]), "nef": len(ext["face"][1]),
+                "np": [int(v.np) for v in gv[:ngrp]], "ne": [int(v.ne) for v in gv[:ngrp]]}
+        return gv, nsol, c, meta, keep + [ext]
+
+    def merge_groups(self, groups: list[dict], comm: dict | None = None) -> dict:
+        """PMMG_merge_grps of a rank's groups (pmx_merge_groups): the merged
+        group stays on the device; merge_fetch returns it, merge_adopt makes it
+        the uploaded group.  groups: the dicts split_fetch returns (tetra_v,
+        xyz, sols, node_index1/2, face_index1/2).  comm: int_node_nitem,
+        int_face_nitem and the external communicators ext_node / ext_face,
+        lists of int_comm_index arrays.  Returns sizes ((4,) int64: np, ne,
+        nnode, nface of the merged group)."""
+        gv, nsol, c, meta, keep = self._merge_views(groups, comm)
+        sz = N.MergeSizes()
+        self._merge = None
+        self._chk(self.lib.pmx_merge_groups(self.ctx, len(groups), gv, nsol, C.byref(c), C.byref(sz)),
+                  "pmx_merge_groups")
+        sizes = np.array([sz.np, sz.ne, sz.nnode, sz.nface], np.int64)
+        self._merge = dict(meta, sizes=sizes)
+        return {"sizes": sizes}
+
+    def merge_fetch(self, data: bool = True) -> dict:
+        """The merged group of the last merge_groups (pmx_merge_fetch): tetra_v
+        ((ne+1, 4), row 0 unused), tet_group, tet_old (ne,), point_group,
+        point_old (np,), node_index1/2, face_index1/2, ext_node_items,
+        ext_face_items (the external communicators' items, concatenated); with
+        data also xyz ((np+1, 3)) and sols ((np+1, size) each)."""
+        mg = getattr(self, "_merge", None)
+        npm, nem, nn, nf = (int(v) for v in mg["sizes"]) if mg else (0, 0, 0, 0)
+        nen, nef = (mg["nen"], mg["nef"]) if mg else (0, 0)
+        d = {"tetra_v": np.empty((nem + 1, 4), np.int32), "tet_group": np.empty(nem, np.int32),
+             "tet_old": np.empty(nem, np.int32), "point_group": np.empty(npm, np.int32),
+             "point_old": np.empty(npm, np.int32), "node_index1": np.empty(nn, np.int32),
+             "node_index2": np.empty(nn, np.int32), "face_index1": np.empty(nf, np.int32),
+             "face_index2": np.empty(nf, np.int32), "ext_node_items": np.empty(nen, np.int32),
+             "ext_face_items": np.empty(nef, np.int32)}
+        d["tetra_v"][0] = 0
+        o = N.MergeOut()
+        for k, a in d.items():
+            setattr(o, k, _ip(a))
+        if data:
+            sizes = mg["sol_sizes"] if mg else []
+            d["xyz"] = np.empty((npm + 1, 3))
+            d["sols"] = [np.empty((npm + 1, s)) for s in sizes]
+            for a in [d["xyz"]] + d["sols"]:
+                a[0] = 0.0
+            o.xyz = _dp(d["xyz"])
+            views = (N.SolView * max(len(sizes), 1))()
+            for i, a in enumerate(d["sols"]):
+                views[i].size = sizes[i]
+                views[i].m = _dp(a)
+            o.nsol = len(sizes)
+            o.sols = views
+        self._chk(self.lib.pmx_merge_fetch(self.ctx, C.byref(o)), "pmx_merge_fetch")
+        return d
+
+    def merge_maps(self, g: int):
+        """Group g's local-to-merged maps (pmx_merge_maps): point_new (np_g,)
+        and tet_new (ne_g,), local entity k at k-1."""
+        mg = getattr(self, "_merge", None)
+        ok = mg is not None and 0 <= g < len(mg["np"])
+        pn = np.empty(mg["np"][g] if ok else 0, np.int32)
+        tn = np.empty(mg["ne"][g] if ok else 0, np.int32)
+        self._chk(self.lib.pmx_merge_maps(self.ctx, g, _ip(pn), _ip(tn)), "pmx_merge_maps")
+        return pn, tn
+
+    def merge_adopt(self, imet: int = 0):
+        """The merged group becomes the uploaded group on the device
+        (pmx_merge_adopt), as upload_background(merged mesh, adja=False) would
+        leave it; imet: index of the metric among the solutions, or -1."""
+        mg = getattr(self, "_merge", None)
+        self._chk(self.lib.pmx_merge_adopt(self.ctx, imet if mg and mg["sol_sizes"] else -1), "pmx_merge_adopt")
+        self._split_sizes = None
+        self.sizes = list(mg["sol_sizes"])
+        self.bg_np, self.bg_ne = int(mg["sizes"][0]), int(mg["sizes"][1])
+
+    def merge_release(self):
+        """Free the merge plan's device memory (pmx_merge_release)."""
+        self._merge = None
+        self._chk(self.lib.pmx_merge_release(self.ctx), "pmx_merge_release")
 
     def upload_new_tets(self, tets: np.ndarray):
         """The new mesh's tets, (ne+1, 4) with 0-based point indices (v[0] < 0:
