@@ -1,0 +1,580 @@
+// pmx_background.hip -- how a mesh becomes the uploaded group (host only).
+//
+// Three entry points install a background: pmx_upload_background (from the
+// host's Mmg arrays), pmx_promote_background (the last step's points and
+// results, already on the device) and pmx_ctx_adopt_group (a merged group on
+// the device).  Each is begin_background, grow_background, its own transfers,
+// build_records, finish_background.  build_records is the one place where
+// connectivity becomes tet records, and the only code that touches d_adja.
+#include <hip/hip_runtime.h>
+#include <atomic>
+#include <cmath>
+#include <cstring>
+
+#include "pmx_transfer.h"
+#include "pmx_kernels.h"
+#include "pmx_internal.h"
+
+namespace {
+
+bool check_background(const pmx_call &C, const pmx_mesh_view *m, int nsol, const pmx_sol_view *sols, int imet) {
+  if (m->np < 1 || m->ne < 1 || m->nt < 0 || m->np >= (1LL << 31) - 1 || 4 * m->ne >= (1LL << 31))
+    return C.fail("mesh sizes out of range");
+  if (!m->point_c || !m->tetra_v || m->point_stride < 24 || m->tetra_stride < 16)
+    return C.fail("point_c / tetra_v missing or strides too small");
+  if (nsol < 0 || nsol > PMX_MAX_SOLS || imet < -1 || imet >= nsol || (nsol > 0 && !sols))
+    return C.fail("bad solution list");
+  for (int s = 0; s < nsol; s++) {
+    if (sols[s].size != 1 && sols[s].size != 3 && sols[s].size != 6) return C.fail("solution size must be 1, 3 or 6");
+    if (!sols[s].m) return C.fail("null solution");
+  }
+  if (m->nt > 0 && (!m->tria_v || !m->adjt || m->tria_stride < 12)) return C.fail("nt > 0 requires tria_v and adjt");
+  return true;
+}
+
+// the interleaved row layout of nsol solutions: offsets and row width
+SolDesc make_sol_desc(int nsol, int imet, const pmx_sol_view *sols) {
+  SolDesc sd{};
+  sd.nsol = nsol;
+  sd.imet = imet;
+  for (int s = 0; s < nsol; s++) {
+    sd.size[s] = sols[s].size;
+    sd.off[s] = sd.S;
+    sd.S += sols[s].size;
+  }
+  return sd;
+}
+
+// boundary triangles of a mesh view -> TriRec records, validated against np
+bool stage_trias(pmx_ctx *ctx, const pmx_mesh_view *m, int64_t np, std::vector<TriRec> &htr) {
+  const int64_t nt = m->nt;
+  htr.assign((size_t)(nt + 1), TriRec{});
+  if (nt < 1) return true;
+  const char *rc = (const char *)m->tria_v;
+  for (int64_t k = 1; k <= nt; k++) {
+    const int *v = (const int *)(rc + k * m->tria_stride);
+    TriRec &r = htr[(size_t)k];
+    for (int l = 0; l < 3; l++) {
+      r.v[l] = v[l];
+      const int a = m->adjt[3 * (k - 1) + 1 + l];
+      r.nb[l] = a / 3;
+      if (v[l] < 1 || v[l] > np || a < 0 || a / 3 > nt) {
+        ctx->err = "tria vertex or adjacency index out of range";
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+// the volume hint grid over the background bbox [lo, hi] (about one cell per
+// 6 tets) and the surface (tria) grid
+bool setup_grids(pmx_ctx *ctx, const double lo[3], const double hi[3], int64_t ne) {
+  double ext[3], vol = 1.0;
+  for (int a = 0; a < 3; a++) {
+    ext[a] = std::max(hi[a] - lo[a], 1e-300);
+    vol *= ext[a];
+  }
+  double target = std::max(1.0, (double)ne / 6.0);
+  double h = std::cbrt(vol / target);
+  GridDesc g;
+  int64_t cells = 1;
+  for (int a = 0; a < 3; a++) {
+    // 1e-9 slack: libm cbrt is not correctly rounded, and 255.00000000000003
+    // cells must stay 255 (r01: C3 got 256 per axis, misaligned with the
+    // mesh: 10% empty cells, 0.73 instead of 0.44 cells start distance)
+    int d = (int)std::ceil(ext[a] / h * (1.0 - 1e-9));
+    d = std::max(1, std::min(d, 4096));
+    g.dim[a] = d;
+    int bits = 0;
+    while ((1 << bits) < d) bits++;
+    g.qf[a] = 21 - bits;
+    g.lo[a] = lo[a];
+    g.inv[a] = (double)d / ext[a];
+    cells *= d;
+  }
+  ctx->grid = g;
+  ctx->gcells = cells;
+  for (int a = 0; a < 3; a++) { ctx->bblo[a] = lo[a]; ctx->bbhi[a] = hi[a]; }
+  if (!ctx->size_tria_grid()) return false;
+  return pmx_dgrow(ctx, ctx->d_grid, (size_t)cells);
+}
+
+// the background's derived layouts, decided per upload / adoption (A/B
+// switches): PMX_WALK_RECORDS=compact builds the
+// walk's 24-B records (a device pass per background: 1.26 ms at C3 for a walk
+// 2 % faster); PMX_HINT_SAMPLE_ORDER=2 the vertex-owner hint sample (three
+// device passes per background, 1.26 ms at C3, for a hint build 0.03 ms
+// faster on a lexicographic numbering).  Defaults: neither -- no device pass
+// per background beyond what every step does.
+bool env_compact_records() {
+  const char *e = getenv("PMX_WALK_RECORDS");
+  return e && strcmp(e, "compact") == 0;
+}
+int env_sample_mode() {
+  const char *e = getenv("PMX_HINT_SAMPLE_ORDER");
+  return (e && atoi(e) == 2) ? 2 : 0;
+}
+
+// ---- the install path: begin, grow, (the caller's transfers), finish -----------
+
+// Whatever happens after this, the context holds no usable background until
+// finish_background has completed: a failed install must not leave sizes that
+// disagree with the device buffers.  Every flag of data derived from the
+// background belongs here and nowhere else (the merge plan does not: it is
+// independent of the background).  layout_env: the records' layout is decided
+// again (a promotion keeps the one its residency build was made for).
+void begin_background(pmx_ctx *ctx, bool layout_env) {
+  ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
+  ctx->have_pmap = ctx->split_valid = false;
+  ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = ctx->bg_btv = false;
+  ctx->stat_np = -1;
+  ctx->eager_nch = 0;
+  if (layout_env) {
+    ctx->compact_recs = env_compact_records();
+    ctx->sample_mode = env_sample_mode();
+  }
+}
+
+// the background's device arrays for np vertices, ne tets, nt trias and rows
+// of S doubles; btv: the connectivity goes to d_btv and the device matches
+// its faces (d_adja grown here, before any copy is in flight)
+bool grow_background(pmx_ctx *ctx, int64_t np, int64_t ne, int64_t nt, int S, bool btv) {
+  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
+  return pmx_dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) && pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) &&
+         (!ctx->compact_recs || pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) &&
+         pmx_dgrow(ctx, ctx->d_wfar, PMX_D_WORDS) && pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) &&
+         pmx_dgrow(ctx, ctx->d_sol, (size_t)(np + 1) * std::max(S, 1)) && pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) &&
+         pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) && pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) &&
+         (!btv || (pmx_dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) && pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5))));
+}
+
+// what an installer hands to finish_background
+struct BgTail {
+  int64_t np, ne, nt;
+  double hausd;
+  const double *lo, *hi;                 // bounding box
+  const std::vector<TriRec> *trias;      // the host's trias, sent here (nullptr: d_tris is set)
+  bool btv;                              // the records were built from d_btv (a FRESH step rebuilds them)
+  bool sample;                           // the owner sample is still to be queued (false: the caller did)
+  hipEvent_t join;                       // records built on another stream: joined before the sync
+};
+
+// The common tail on the call's stream: sizes, grids, owner sample, trias, fan
+// check, one sync, the non-manifold check; the background is usable after it.
+// (The node -> trias fans are the step's: PMMG_precompute_nodeTrias runs
+// inside the reference's call.)
+bool finish_background(const pmx_call &C, const BgTail &t, Trace &tr) {
+  pmx_ctx *ctx = C.ctx;
+  ctx->np = t.np; ctx->ne = t.ne; ctx->nt = t.nt; ctx->hausd = t.hausd;
+  if (!setup_grids(ctx, t.lo, t.hi, t.ne)) return false;
+  if (t.sample && !ctx->order_hint_samples(t.ne, t.np, C.s)) return false;
+  tr.mark("grids");
+  if (t.trias)
+    PMX_CK(C, hipMemcpyAsync(ctx->d_tris.p, t.trias->data(), t.trias->size() * sizeof(TriRec), hipMemcpyHostToDevice, C.s));
+  if (!ctx->check_fans(C.s)) return false;
+  if (t.join) PMX_CK(C, hipStreamWaitEvent(C.s, t.join, 0));
+  PMX_CK(C, hipGetLastError());
+  tr.mark("trias + topology");
+  PMX_CK(C, hipStreamSynchronize(C.s));   // the caller's host staging dies after this
+  tr.mark("sync");
+  if (ctx->h_nbad.p[PMX_H_NONMANIFOLD]) return C.fail("non-manifold tet faces");
+  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad.p[PMX_H_BAD_FANS] == 0;
+  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[PMX_H_NSAMP] : 0;
+  ctx->bg_btv = t.btv;
+  ctx->have_bg = true;
+  return true;
+}
+
+}  // namespace
+
+// ---- tet records -----------------------------------------------------------------
+
+// tv == nullptr: dst's 32-B records are in place (the host packed them); only
+// the compact records are built.  d_adja and the face matching's scratch are
+// shared by the builds on the main and the topo stream (an upload, a FRESH
+// step's rederive, the residency build): each build waits for the one before
+// it in enqueue order and records ev_adja once it no longer reads them.
+bool pmx_ctx::build_records(const int4 *tv, const int *host_adja, int64_t ne, int64_t np, const RecordSet &dst,
+                            hipStream_t s) {
+  const pmx_call C{this, "tet records", s};
+  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
+  if (!pmx_dgrow(this, *dst.tets, (size_t)(ne + 1)) || (compact_recs && !pmx_dgrow(this, *dst.wrec, (size_t)(ne + 1))) ||
+      !pmx_dgrow(this, d_wfar, PMX_D_WORDS) || !pmx_dgrow(this, *dst.sample, (size_t)std::max<int64_t>(ns, 1)))
+    return false;
+  if (!tv || host_adja) h_nbad.p[dst.h_nonmanifold] = 0;   // no face matching
+  if (tv) {
+    if (!pmx_dgrow(this, d_adja, (size_t)(4 * ne + 5))) return false;
+    if (ev_adja.e) PMX_CK(C, hipStreamWaitEvent(s, ev_adja, 0));
+    if (host_adja)
+      PMX_CK(C, hipMemcpyAsync(d_adja.p, host_adja, (size_t)(4 * ne + 5) * sizeof(int), hipMemcpyHostToDevice, s));
+    else if (!pmx_ctx_build_adja_device(this, tv, ne, np, d_adja.p, s, h_nbad.p + dst.h_nonmanifold))
+      return false;
+    launch_build_tetrec(tv, d_adja.p, ne, PMX_HINT_STRIDE, dst.tets->p, dst.sample->p, s);
+    if (!ev_adja.create(false)) return C.fail("creating the adjacency event");
+    PMX_CK(C, hipEventRecord(ev_adja, s));
+  }
+  if (compact_recs) launch_build_wrec(dst.tets->p, ne, dst.wrec->p, d_wfar.p + dst.d_far, h_nbad.p + dst.h_far, s);
+  else h_nbad.p[dst.h_far] = 0;                            // no far fields unless compact records are built
+  return true;
+}
+
+// The hint sample, once the tets are on the device and np set
+// (sample_mode, PMX_HINT_SAMPLE_ORDER at the upload): 0 every 4th tet in tet
+// order, packed with the tet records (nothing to do here); 2 one tet per
+// vertex, in vertex order (k_vmin_owner; its count lands in h_nbad[PMX_H_NSAMP],
+// nsamp after the upload's sync) -- A/Bs in DESIGN.md section 7 r05 / r06.  (r05's
+// mode 1, the every-4th-tet sample sorted by smallest vertex, was dropped in
+// r06: its sort could not be redone by a FRESH step.)
+bool pmx_ctx::order_hint_samples(int64_t ne, int64_t np, hipStream_t s) {
+  samples_sorted = samples_owner = false;
+  if (sample_mode != 2 || np < 1 || ne < 1) return true;
+  const size_t tb = owner_scan_temp_bytes(np);
+  if (!pmx_dgrow(this, d_skey, (size_t)(np + 2)) || !pmx_dgrow(this, d_sidx, (size_t)(2 * (np + 1))) ||
+      !pmx_dgrow(this, d_salt, (size_t)(np + 1)) || !pmx_dgrow(this, d_tets_sk, (size_t)(np + 1)) ||
+      !pmx_dgrow(this, d_stmp, std::max<size_t>(tb, 1)) || !pmx_dgrow(this, d_wfar, PMX_D_WORDS))
+    return false;
+  if (!launch_owner_sample(d_tets.p, ne, np, d_skey.p, d_sidx.p, d_sidx.p + (np + 1), d_salt.p, d_tets_sk.p,
+                           d_wfar.p + PMX_D_NSAMP, h_nbad.p + PMX_H_NSAMP, d_stmp.p, tb, s)) {
+    err = "hint sample: vertex owners";
+    return false;
+  }
+  std::swap(d_tets_s, d_salt);
+  samples_sorted = samples_owner = true;
+  return true;
+}
+
+// PMX_RUN_FRESH_BACKGROUND: the device passes an upload runs on the raw
+// arrays, again, in stream order on s -- a ParMmg iteration brings a new
+// background (PMMG_update_oldGrps, src/libparmmg1.c:653) and the reference
+// recomputes its derived data inside the call (src/interpmesh_pmmg.c:514-518):
+// the face matching of the uploaded connectivity with the tet records and the
+// every-4th-tet sample (MMG3D_hashTetra's adjacency on the device) when the
+// device built them, the compact records, the owner sample
+bool pmx_ctx::rederive(hipStream_t s) {
+  if (!build_records(bg_btv ? d_btv.p : nullptr, nullptr, ne, np, records_current(), s)) return false;
+  if (sample_mode == 2 && !order_hint_samples(ne, np, s)) return false;
+  return pmx_call{this, "pmx_run", s}.hip(hipGetLastError(), "background records");
+}
+
+// ---- the three installers ----------------------------------------------------------
+
+extern "C" {
+
+int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
+                          const pmx_sol_view *sols, int imet) {
+  if (!ctx) return 0;
+  const pmx_call C{ctx, "pmx_upload_background", ctx->stream};
+  begin_background(ctx, true);
+  if (!m) return C.fail("null mesh");
+  hipSetDevice(ctx->device);
+  if (!check_background(C, m, nsol, sols, imet)) return 0;
+  const int64_t np = m->np, ne = m->ne, nt = m->nt;
+  const bool dev_adja = m->adja == nullptr;   // no MMG3D_hashTetra on the host: device face matching
+  // the host packs the every-4th-tet hint sample with the tet records (the
+  // device-adjacency path: k_build_tetrec writes it)
+  const bool host_sample = !dev_adja && ctx->sample_mode == 0;
+  Trace tr("background");
+  const SolDesc sd = make_sol_desc(nsol, imet, sols);
+  const int S = sd.S;
+  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
+  const size_t hs_n = (size_t)(np + 1) * std::max(S, 1);
+  // pinned staging: xyz | tets (TetRec, or int4 when the device builds the
+  // adjacency) | packed hint sample | solutions; each part goes down as soon
+  // as it is packed (the tets in chunks), one sync at the end
+  const size_t trec = dev_adja ? sizeof(int4) : sizeof(TetRec);
+  const size_t o_p = 0, o_t = o_p + pmx_call::al256((size_t)(np + 1) * 24),
+               o_h = o_t + pmx_call::al256((size_t)(ne + 1) * trec),
+               o_s = o_h + pmx_call::al256(host_sample ? (size_t)ns * sizeof(int4) : 0),
+               total = o_s + pmx_call::al256(hs_n * sizeof(double));
+  PMX_CK(C, hipStreamSynchronize(ctx->stream));   // the arena may still feed an earlier copy
+  char *stg = pmx_hstage(ctx, total);
+  if (!stg) return 0;
+  // any return after the topology fork first waits for that stream (a later
+  // call may regrow the buffers its kernels use)
+  struct StreamGuard {
+    hipStream_t s = nullptr;
+    ~StreamGuard() { if (s) hipStreamSynchronize(s); }
+  } topo_guard;
+  if (!grow_background(ctx, np, ne, nt, S, dev_adja)) return 0;
+  hipStream_t st = ctx->stream;
+
+  // points -> dense xyz (24 B), bounding box per chunk
+  double *hp = (double *)(stg + o_p);
+  hp[0] = hp[1] = hp[2] = 0.0;
+  const char *pc = (const char *)m->point_c;
+  double blo[64][3], bhi[64][3];
+  const int nch = par_chunks(1, np + 1, [&](int c, int64_t i0, int64_t i1) {
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (int64_t i = i0; i < i1; i++) {
+      const double *cc = (const double *)(pc + i * m->point_stride);
+      for (int a = 0; a < 3; a++) {
+        hp[3 * i + a] = cc[a];
+        lo[a] = std::min(lo[a], cc[a]);
+        hi[a] = std::max(hi[a], cc[a]);
+      }
+    }
+    for (int a = 0; a < 3; a++) { blo[c][a] = lo[a]; bhi[c][a] = hi[a]; }
+  });
+  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+  for (int c = 0; c < nch; c++)
+    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], blo[c][a]); hi[a] = std::max(hi[a], bhi[c][a]); }
+  PMX_CK(C, hipMemcpyAsync(ctx->d_xyz.p, hp, (size_t)(np + 1) * 24, hipMemcpyHostToDevice, st));
+  tr.mark("points");
+  // tets -> TetRec with neighbour tet index (or the bare connectivity), + the
+  // packed hint sample (the connectivity of every PMX_HINT_STRIDE-th tet,
+  // contiguous: the hint build streams ne/4 * 16 B instead of touching every
+  // line of the tet records); in chunks, each DMA'd while the next is packed
+  TetRec *ht = (TetRec *)(stg + o_t);
+  int4 *htv = (int4 *)(stg + o_t);
+  int4 *hh = (int4 *)(stg + o_h);
+  if (dev_adja) htv[0] = make_int4(0, 0, 0, 0);
+  else memset(&ht[0], 0, sizeof(TetRec));
+  const char *tc = (const char *)m->tetra_v;
+  const int *adja_in = m->adja;
+  bool bad = false;
+  const int64_t ntc = std::max<int64_t>(1, std::min<int64_t>(8, ne >> 20));
+  for (int64_t c = 0; c < ntc; c++) {
+    const int64_t klo = (c == 0) ? 0 : 1 + ne * c / ntc, khi = 1 + ne * (c + 1) / ntc;
+    par_for(std::max<int64_t>(klo, 1), khi, [&](int64_t k0, int64_t k1) {
+      bool b = false;
+      for (int64_t k = k0; k < k1; k++) {
+        const int *v = (const int *)(tc + k * m->tetra_stride);
+        // indices the kernels will gather through: a valid tet (v[0] > 0,
+        // MG_EOK) must name vertices 1..np and neighbours 0..ne
+        const bool valid = v[0] > 0;
+        if (dev_adja) {
+          if (!valid) { st4(&htv[k], 0, 0, 0, 0); }
+          else {
+            for (int l = 0; l < 4; l++)
+              if (v[l] < 1 || v[l] > np) b = true;
+            st4(&htv[k], v[0], v[1], v[2], v[3]);
+          }
+        } else {
+          TetRec &r = ht[(size_t)k];
+          for (int l = 0; l < 4; l++) {
+            r.v[l] = v[l];
+            const int a = adja_in[4 * (k - 1) + 1 + l];
+            r.nb[l] = a / 4;
+            if (valid && (v[l] < 1 || v[l] > np || a < 0 || a / 4 > ne)) b = true;
+          }
+        }
+        if (host_sample && (k - 1) % PMX_HINT_STRIDE == 0)
+          hh[(k - 1) / PMX_HINT_STRIDE] = make_int4(v[0], v[1], v[2], v[3]);
+      }
+      if (b) __atomic_store_n(&bad, true, __ATOMIC_RELAXED);
+      std::atomic_thread_fence(std::memory_order_seq_cst);
+    });
+    if (bad) break;
+    if (dev_adja)
+      PMX_CK(C, hipMemcpyAsync(ctx->d_btv.p + klo, htv + klo, (size_t)(khi - klo) * sizeof(int4), hipMemcpyHostToDevice, st));
+    else
+      PMX_CK(C, hipMemcpyAsync(ctx->d_tets.p + klo, ht + klo, (size_t)(khi - klo) * sizeof(TetRec), hipMemcpyHostToDevice, st));
+  }
+  if (bad) return C.fail("tet vertex or adjacency index out of range");
+  // the records (the host's: only their compact copy) and the owner sample
+  // (mode 2) while the host packs the solutions and trias.  With the device's
+  // face matching they run on the topology stream as soon as the connectivity
+  // is down, overlapping that packing and its DMA; joined before the final sync
+  hipStream_t rs = st;
+  if (dev_adja) {
+    PMX_CK(C, hipEventRecord(ctx->ev_fork, st));
+    PMX_CK(C, hipStreamWaitEvent(ctx->topo, ctx->ev_fork, 0));
+    topo_guard.s = rs = ctx->topo;
+  } else if (host_sample) {
+    PMX_CK(C, hipMemcpyAsync(ctx->d_tets_s.p, hh, (size_t)ns * sizeof(int4), hipMemcpyHostToDevice, st));
+  }
+  if (!ctx->build_records(dev_adja ? ctx->d_btv.p : nullptr, nullptr, ne, np, ctx->records_current(), rs) ||
+      !ctx->order_hint_samples(ne, np, rs))
+    return 0;
+  if (dev_adja) PMX_CK(C, hipEventRecord(ctx->ev_join, ctx->topo));
+  tr.mark("tets");
+  // solutions -> interleaved [np+1][S], in blocks of 1024 rows (each row's
+  // line written while it is in cache, not once per solution) and chunks
+  // whose DMA overlaps the packing of the next
+  double *hs = (double *)(stg + o_s);
+  // row 0: Mmg's unused slot, as the caller holds it (no kernel reads a
+  // vertex 0 -- but PMMG_prilen's parallel edges with a tensor metric and
+  // metRidTyp = 1 read met->m[ip] flat, src/quality_pmmg.c:466, i.e. row 0
+  // for ip < 6)
+  memset(hs, 0, (size_t)std::max(S, 1) * sizeof(double));
+  for (int s = 0; s < nsol; s++)
+    for (int j = 0; j < sols[s].size; j++) hs[sd.off[s] + j] = sols[s].m[j];
+  if (S == 0) {
+    memset(hs, 0, hs_n * sizeof(double));
+    PMX_CK(C, hipMemcpyAsync(ctx->d_sol.p, hs, hs_n * sizeof(double), hipMemcpyHostToDevice, st));
+  } else {
+    const int64_t nsc = std::max<int64_t>(1, std::min<int64_t>(4, (np * S) >> 21));
+    for (int64_t c = 0; c < nsc; c++) {
+      const int64_t r0 = (c == 0) ? 0 : 1 + np * c / nsc, r1 = 1 + np * (c + 1) / nsc;
+      par_for(std::max<int64_t>(r0, 1), r1, [&](int64_t i0, int64_t i1) {
+        for (int64_t b0 = i0; b0 < i1; b0 += 1024) {
+          const int64_t b1 = std::min(i1, b0 + 1024);
+          for (int s = 0; s < nsol; s++) {
+            const int sz = sols[s].size, off = sd.off[s];
+            const double *src = sols[s].m;
+            for (int64_t i = b0; i < b1; i++)
+              for (int j = 0; j < sz; j++) hs[(size_t)i * S + off + j] = src[i * sz + j];
+          }
+        }
+      });
+      PMX_CK(C, hipMemcpyAsync(ctx->d_sol.p + r0 * S, hs + r0 * S, (size_t)((r1 - r0) * S) * sizeof(double),
+                               hipMemcpyHostToDevice, st));
+    }
+  }
+  tr.mark("solutions");
+  // boundary triangles
+  std::vector<TriRec> htr;
+  if (!stage_trias(ctx, m, np, htr)) return 0;
+  ctx->sd = sd;
+  return finish_background(C, {np, ne, nt, m->hausd, lo, hi, &htr, dev_adja, false, dev_adja ? ctx->ev_join.e : nullptr}, tr);
+}
+
+// The last step's points, results and new tets become the background (device
+// residency across ParMmg iterations, pmx_capi.hip): only the boundary trias
+// and the rows the step did not write come from the host.
+
+int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const pmx_sol_view *sols) {
+  if (!ctx) return 0;
+  const pmx_call C{ctx, "pmx_promote_background", ctx->stream};
+  if (!m) return C.fail("null mesh");
+  if (!ctx->ran || !ctx->have_pts || ctx->out_n != ctx->nq || ctx->out_S != ctx->sd.S)
+    return C.fail("no step has run on the current uploads");
+  if (!ctx->have_ntet) return C.fail("upload the new tets first");
+  if (ctx->pts_first != 1) return C.fail("the points view must start at 1 (Mmg numbering)");
+  const int64_t n = ctx->nq, ne = ctx->n_ntet, nt = m->nt;
+  if (m->np != n || m->ne != ne || n < 1) return C.fail("mesh sizes differ from the uploaded points / new tets");
+  if (nt < 0 || (nt > 0 && (!m->tria_v || !m->adjt || m->tria_stride < 12)))
+    return C.fail("nt > 0 requires tria_v and adjt");
+  const SolDesc sd = ctx->sd;
+  if (nsol != sd.nsol || (nsol > 0 && !sols)) return C.fail("solution list differs from the step's");
+  for (int s = 0; s < nsol; s++)
+    if (sols[s].size != sd.size[s]) return C.fail("solution size differs from the step's");
+  if (m->adja) {
+    // the walks gather through these: every neighbour of a valid tet must
+    // name a face of 1..ne (as pmx_upload_background checks)
+    bool badj = false;
+    par_chunks(1, ne + 1, [&](int, int64_t k0, int64_t k1) {
+      bool b = false;
+      for (int64_t k = k0; k < k1 && !b; k++) {
+        if (m->tetra_v && *(const int *)((const char *)m->tetra_v + k * m->tetra_stride) <= 0) continue;
+        for (int f = 0; f < 4; f++) {
+          const int a = m->adja[4 * (k - 1) + 1 + f];
+          if (a < 0 || a / 4 > ne) b = true;
+        }
+      }
+      if (b) __atomic_store_n(&badj, true, __ATOMIC_RELAXED);
+    });
+    if (badj) return C.fail("adjacency entry out of range");
+  }
+  hipSetDevice(ctx->device);
+  Trace tr("promote");
+  hipStream_t st = ctx->stream;
+  if (!ctx->fix_orphans() || !ctx->ensure_tets(st)) return 0;
+  PMX_CK(C, hipStreamSynchronize(st));
+  if (!ctx->check_device_errors()) return 0;
+  tr.mark("sync");
+  const int S = sd.S;
+  // rows the step did not write keep the caller's values (Mmg's own, or the
+  // frozen-point copy): which ones, from the write masks
+  char *stg = pmx_hstage(ctx, (size_t)n);
+  if (!stg) return 0;
+  PMX_CK(C, hipMemcpyAsync(stg, ctx->d_wmask.p, (size_t)n, hipMemcpyDeviceToHost, st));
+  PMX_CK(C, hipStreamSynchronize(st));
+  const uint8_t *wm = (const uint8_t *)stg;
+  const unsigned full = (1u << nsol) - 1u;
+  // per chunk, then concatenated in chunk order
+  std::vector<std::vector<int4>> cent(64);
+  std::vector<std::vector<double>> cval(64);
+  bool missing = false;
+  const int nch = par_chunks(0, n, [&](int c, int64_t j0, int64_t j1) {
+    for (int64_t j = j0; j < j1; j++) {
+      if ((wm[j] & full) == full) continue;      // every solution written (the common case)
+      for (int s = 0; s < nsol; s++) {
+        if (wm[j] & (1u << s)) continue;
+        const int sz = sd.size[s];
+        if (!sols[s].m) { __atomic_store_n(&missing, true, __ATOMIC_RELAXED); continue; }
+        cent[(size_t)c].push_back(make_int4((int)(j + 1), sd.off[s], sz, 0));
+        const double *src = sols[s].m + j * sz;   // pmx_download's layout
+        for (int q = 0; q < 6; q++) cval[(size_t)c].push_back(q < sz ? src[q] : 0.0);
+      }
+    }
+  });
+  if (missing) return C.fail("a row the step did not write needs the caller's solution");
+  std::vector<int4> ent;
+  std::vector<double> vals;
+  for (int c = 0; c < nch; c++) {
+    ent.insert(ent.end(), cent[(size_t)c].begin(), cent[(size_t)c].end());
+    vals.insert(vals.end(), cval[(size_t)c].begin(), cval[(size_t)c].end());
+  }
+  tr.mark("unwritten rows");
+  // boundary trias of the new mesh (the host's: Mmg's numbering)
+  std::vector<TriRec> htr;
+  if (!stage_trias(ctx, m, n, htr)) return 0;
+  tr.mark("trias");
+  // nothing has moved so far: a promotion refused above leaves the step
+  // promotable.  From here on the background is invalid until this completes
+  begin_background(ctx, false);
+  if (!grow_background(ctx, n, ne, nt, S, false)) return 0;
+  const bool tags = ctx->have_qtag;
+  if (tags && !pmx_dgrow(ctx, ctx->d_ptag, (size_t)(n + 1))) return 0;
+  launch_promote(ctx->d_qxyz.p, ctx->d_out.p, tags ? ctx->d_qtag.p : nullptr, n, S, ctx->d_xyz.p, ctx->d_sol.p,
+                 tags ? ctx->d_ptag.p : nullptr, st);
+  if (!ent.empty()) {
+    if (!pmx_dgrow(ctx, ctx->d_pent, ent.size()) || !pmx_dgrow(ctx, ctx->d_pval, vals.size())) return 0;
+    PMX_CK(C, hipMemcpyAsync(ctx->d_pent.p, ent.data(), ent.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+    PMX_CK(C, hipMemcpyAsync(ctx->d_pval.p, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_patch_rows(ctx->d_pent.p, ctx->d_pval.p, (int64_t)ent.size(), S, ctx->d_sol.p, st);
+  }
+  tr.mark("promote launch");
+  // tet records: the set prepared while the step ran (residency on) is swapped
+  // in with its counts, once its build has finished -- else they are built
+  // from the caller's Mmg adjacency (mesh->adja after remeshing) or from the
+  // device's face matching (a residency build still running is then left to
+  // finish behind ev_adja: its result is dropped)
+  const bool prepared = ctx->next_topo && !m->adja;
+  ctx->next_topo = false;
+  if (prepared) {
+    PMX_CK(C, hipEventSynchronize(ctx->ev_topo));
+    tr.mark("wait topo");
+    std::swap(ctx->d_tets, ctx->d_tets_next);
+    std::swap(ctx->d_wrec, ctx->d_wrec_next);
+    std::swap(ctx->d_tets_s, ctx->d_tets_s_next);
+    ctx->h_nbad.p[PMX_H_NONMANIFOLD] = ctx->h_nbad.p[PMX_H_NONMANIFOLD_NEXT];
+    ctx->h_nbad.p[PMX_H_FAR] = ctx->h_nbad.p[PMX_H_FAR_NEXT];
+  } else if (!ctx->build_records(ctx->d_ntetv.p, m->adja, ne, n, ctx->records_current(), st)) {
+    return 0;
+  }
+  tr.mark("tet records");
+  // (records from the new tets or the caller's adja, not d_btv: a FRESH step keeps them)
+  if (!finish_background(C, {n, ne, nt, m->hausd, ctx->qlo, ctx->qhi, &htr, false, true, nullptr}, tr)) return 0;
+  ctx->have_ptag = tags;
+  // the points and the results were consumed: the next step needs new points
+  ctx->have_pts = ctx->ran = ctx->have_ntet = false;
+  return 1;
+}
+
+}  // extern "C"
+
+// A device-resident group as the background (pmx_merge_adopt):
+// pmx_upload_background's device-adjacency path with nt = 0, its host packing
+// and DMA replaced by device-to-device copies
+bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
+                         const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]) {
+  const pmx_call C{ctx, who, ctx->stream};
+  begin_background(ctx, true);
+  if (np < 1 || ne < 1 || np >= (1LL << 31) - 1 || 4 * ne >= (1LL << 31)) return C.fail("mesh sizes out of range");
+  if (!grow_background(ctx, np, ne, 0, sd.S, true)) return false;
+  hipStream_t st = ctx->stream;
+  const size_t hs_n = (size_t)(np + 1) * std::max(sd.S, 1);
+  if (!C.hip(hipMemcpyAsync(ctx->d_xyz.p, xyz, (size_t)(np + 1) * 24, hipMemcpyDeviceToDevice, st), "points") ||
+      !C.hip(hipMemcpyAsync(ctx->d_btv.p, tv, (size_t)(ne + 1) * sizeof(int4), hipMemcpyDeviceToDevice, st), "tets") ||
+      !C.hip(sd.S > 0 ? hipMemcpyAsync(ctx->d_sol.p, sol, hs_n * sizeof(double), hipMemcpyDeviceToDevice, st)
+                      : hipMemsetAsync(ctx->d_sol.p, 0, hs_n * sizeof(double), st), "solutions") ||
+      !C.hip(hipMemsetAsync(ctx->d_tris.p, 0, sizeof(TriRec), st), "trias"))
+    return false;
+  if (!ctx->build_records(ctx->d_btv.p, nullptr, ne, np, ctx->records_current(), st)) return false;
+  ctx->sd = sd;
+  Trace tr("adopt");
+  return finish_background(C, {np, ne, 0, 0.0, lo, hi, nullptr, true, true, nullptr}, tr);
+}

@@ -1,8 +1,9 @@
 // pmx_capi.hip -- host side of the C ABI declared in include/pmx_transfer.h.
 //
-// Converts Mmg-style AoS (strided) meshes and solutions into the SoA device
-// layout of pmx_device.h, owns the device buffers of one GPU, and sequences
-// the kernels of one transfer step on one HIP stream.
+// The context's life, the new points' upload, the step (pmx_run: the kernels
+// of one transfer step sequenced on the context's streams), the downloads, the
+// device alloc / free ABI and the host pool.  How a mesh becomes the uploaded
+// group -- upload, promotion, adoption, the tet records -- is pmx_background.hip.
 #include <hip/hip_runtime.h>
 #include <sched.h>
 #include <algorithm>
@@ -77,7 +78,7 @@ static unsigned cpu_share() {
 // quota of 256, C3 resident cycle, tools/trace_resident.py): 8 threads 89-95
 // ms, 16 threads 67-71 ms, 24 threads (throttled by the quota) 77 ms.
 // Ranges below PMX_HOST_THREADS_MIN elements (default 2^18) stay serial.
-static unsigned host_threads() {
+unsigned pmx_host_threads() {
   static const unsigned T = [] {
     const char *e = getenv("PMX_HOST_THREADS");
     unsigned t = e ? (unsigned)std::max(1, atoi(e)) : cpu_share();
@@ -85,42 +86,15 @@ static unsigned host_threads() {
   }();
   return T;
 }
-// streaming (non-temporal) 16-B stores into the pinned staging: the host
-// never reads those lines again, and a plain store first reads each line for
-// ownership (a third of the packing traffic).  A pass ends with a full fence
-// before its DMA is issued.
-typedef int pmx_v4i __attribute__((ext_vector_type(4)));
-static inline void st4(int4 *p, int a, int b, int c, int d) {
-  const pmx_v4i v = {a, b, c, d};
-  __builtin_nontemporal_store(v, (pmx_v4i *)p);
-}
-static int64_t host_threads_min() {
+int64_t pmx_host_threads_min() {
   static const int64_t M = [] {
     const char *e = getenv("PMX_HOST_THREADS_MIN");
     return e ? std::max<int64_t>(1, atoll(e)) : (int64_t)(1 << 18);
   }();
   return M;
 }
-// PMX_TRACE=1: host phase timings of the staging calls on stderr
-namespace {
-struct Trace {
-  const char *who;
-  bool on;
-  std::chrono::steady_clock::time_point t0, last;
-  explicit Trace(const char *w) : who(w), on(getenv("PMX_TRACE") != nullptr) {
-    if (on) t0 = last = std::chrono::steady_clock::now();
-  }
-  void mark(const char *what) {
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[pmx] %s %-22s %8.3f ms\n", who, what,
-            std::chrono::duration<double, std::milli>(now - last).count());
-    last = now;
-  }
-};
-}  // namespace
 
-// a persistent pool of host_threads()-1 workers (thread creation per pass
+// a persistent pool of pmx_host_threads()-1 workers (thread creation per pass
 // cost ~0.1 ms per pass and dominated the chunked copies); the calling thread
 // takes part.  One job at a time (a mutex serialises concurrent callers).
 namespace {
@@ -188,27 +162,12 @@ struct HostPool {
   }
 };
 HostPool &host_pool() {
-  static HostPool *p = new HostPool(host_threads() - 1);   // never destroyed: no exit-time joins
+  static HostPool *p = new HostPool(pmx_host_threads() - 1);   // never destroyed: no exit-time joins
   return *p;
 }
 }  // namespace
+void pmx_host_pool_run(const std::function<void(int)> &job, int n) { host_pool().run(job, n); }
 
-// f(chunk, lo, hi) over C contiguous chunks of [lo, hi); returns C
-template <class F> static int par_chunks(int64_t lo, int64_t hi, F f) {
-  const int64_t n = hi - lo;
-  const int C = (host_threads() <= 1 || n < host_threads_min()) ? 1 : (int)host_threads();
-  if (C == 1) { f(0, lo, hi); return 1; }
-  const int64_t chunk = (n + C - 1) / C;
-  const std::function<void(int)> job = [&](int i) {
-    const int64_t a = lo + (int64_t)i * chunk, b = std::min(hi, a + chunk);
-    f(i, a, std::max(a, b));
-  };
-  host_pool().run(job, C);
-  return C;
-}
-template <class F> static void par_for(int64_t lo, int64_t hi, F f) {
-  par_chunks(lo, hi, [&](int, int64_t a, int64_t b) { if (a < b) f(a, b); });
-}
 void pmx_par_for(int64_t lo, int64_t hi, const std::function<void(int64_t, int64_t)> &f) {
   par_for(lo, hi, f);
 }
@@ -285,77 +244,6 @@ bool pmx_ctx::check_device_errors() {
   return true;
 }
 
-// boundary triangles of a mesh view -> TriRec records, validated against np
-static bool stage_trias(pmx_ctx *ctx, const pmx_mesh_view *m, int64_t np, std::vector<TriRec> &htr) {
-  const int64_t nt = m->nt;
-  htr.assign((size_t)(nt + 1), TriRec{});
-  if (nt < 1) return true;
-  const char *rc = (const char *)m->tria_v;
-  for (int64_t k = 1; k <= nt; k++) {
-    const int *v = (const int *)(rc + k * m->tria_stride);
-    TriRec &r = htr[(size_t)k];
-    for (int l = 0; l < 3; l++) {
-      r.v[l] = v[l];
-      const int a = m->adjt[3 * (k - 1) + 1 + l];
-      r.nb[l] = a / 3;
-      if (v[l] < 1 || v[l] > np || a < 0 || a / 3 > nt) {
-        ctx->err = "tria vertex or adjacency index out of range";
-        return false;
-      }
-    }
-  }
-  return true;
-}
-
-// the volume hint grid over the background bbox [lo, hi] (about one cell per
-// 6 tets) and the surface (tria) grid
-static bool setup_grids(pmx_ctx *ctx, const double lo[3], const double hi[3], int64_t ne) {
-  double ext[3], vol = 1.0;
-  for (int a = 0; a < 3; a++) {
-    ext[a] = std::max(hi[a] - lo[a], 1e-300);
-    vol *= ext[a];
-  }
-  double target = std::max(1.0, (double)ne / 6.0);
-  double h = std::cbrt(vol / target);
-  GridDesc g;
-  int64_t cells = 1;
-  for (int a = 0; a < 3; a++) {
-    // 1e-9 slack: libm cbrt is not correctly rounded, and 255.00000000000003
-    // cells must stay 255 (r01: C3 got 256 per axis, misaligned with the
-    // mesh: 10% empty cells, 0.73 instead of 0.44 cells start distance)
-    int d = (int)std::ceil(ext[a] / h * (1.0 - 1e-9));
-    d = std::max(1, std::min(d, 4096));
-    g.dim[a] = d;
-    int bits = 0;
-    while ((1 << bits) < d) bits++;
-    g.qf[a] = 21 - bits;
-    g.lo[a] = lo[a];
-    g.inv[a] = (double)d / ext[a];
-    cells *= d;
-  }
-  ctx->grid = g;
-  ctx->gcells = cells;
-  for (int a = 0; a < 3; a++) { ctx->bblo[a] = lo[a]; ctx->bbhi[a] = hi[a]; }
-  if (!ctx->size_tria_grid()) return false;
-  return pmx_dgrow(ctx, ctx->d_grid, (size_t)cells);
-}
-
-// the background's derived layouts, decided per upload / promotion (A/B
-// switches): PMX_WALK_RECORDS=compact builds the
-// walk's 24-B records (a device pass per background: 1.26 ms at C3 for a walk
-// 2 % faster); PMX_HINT_SAMPLE_ORDER=2 the vertex-owner hint sample (three
-// device passes per background, 1.26 ms at C3, for a hint build 0.03 ms
-// faster on a lexicographic numbering).  Defaults: neither -- no device pass
-// per background beyond what every step does.
-static bool env_compact_records() {
-  const char *e = getenv("PMX_WALK_RECORDS");
-  return e && strcmp(e, "compact") == 0;
-}
-static int env_sample_mode() {
-  const char *e = getenv("PMX_HINT_SAMPLE_ORDER");
-  return (e && atoi(e) == 2) ? 2 : 0;
-}
-
 extern "C" {
 
 pmx_ctx *pmx_create(int device) {
@@ -384,7 +272,7 @@ pmx_ctx *pmx_create(int device) {
   ctx->stream = ctx->own;
   if (!sok ||
       !ctx->ev_topo.create(false) || !ctx->ev_tets.create(false) ||
-      ctx->h_nbad.grow(8 * sizeof(unsigned), 8 * sizeof(unsigned)) != hipSuccess ||
+      ctx->h_nbad.grow(PMX_H_WORDS * sizeof(unsigned), PMX_H_WORDS * sizeof(unsigned)) != hipSuccess ||
       !pmx_create_events(ctx->ev_dl, false) || !pmx_create_events(ctx->ev_eg, false) ||
       !ctx->ev_fork.create(false) || !ctx->ev_fork2.create(false) || !ctx->ev_join.create(false)) {
     pmx_destroy(ctx);
@@ -447,268 +335,6 @@ int pmx_device_info(pmx_ctx *ctx, char *buf, int buflen) {
   CK(hipGetDeviceProperties(&p, ctx->device));
   snprintf(buf, (size_t)buflen, "%s %s CUs=%d HBM=%.1fGB", p.name, p.gcnArchName,
            p.multiProcessorCount, (double)p.totalGlobalMem / 1e9);
-  return 1;
-}
-
-// ---- background upload ------------------------------------------------------
-
-static bool check_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const pmx_sol_view *sols,
-                             int imet) {
-  if (m->np < 1 || m->ne < 1 || m->nt < 0 || m->np >= (1LL << 31) - 1 || 4 * m->ne >= (1LL << 31)) {
-    ctx->err = "pmx_upload_background: mesh sizes out of range";
-    return false;
-  }
-  if (!m->point_c || !m->tetra_v || m->point_stride < 24 || m->tetra_stride < 16) {
-    ctx->err = "pmx_upload_background: point_c / tetra_v missing or strides too small";
-    return false;
-  }
-  if (nsol < 0 || nsol > PMX_MAX_SOLS || imet < -1 || imet >= nsol || (nsol > 0 && !sols)) {
-    ctx->err = "pmx_upload_background: bad solution list";
-    return false;
-  }
-  for (int s = 0; s < nsol; s++) {
-    if (sols[s].size != 1 && sols[s].size != 3 && sols[s].size != 6) {
-      ctx->err = "pmx_upload_background: solution size must be 1, 3 or 6";
-      return false;
-    }
-    if (!sols[s].m) {
-      ctx->err = "pmx_upload_background: null solution";
-      return false;
-    }
-  }
-  if (m->nt > 0 && (!m->tria_v || !m->adjt || m->tria_stride < 12)) {
-    ctx->err = "pmx_upload_background: nt > 0 requires tria_v and adjt";
-    return false;
-  }
-  return true;
-}
-
-int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
-                          const pmx_sol_view *sols, int imet) {
-  if (!ctx) return 0;
-  // whatever happens below, the context holds no usable background until the
-  // upload has completed (a failed call must not leave sizes that disagree
-  // with the device buffers)
-  ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
-  ctx->have_pmap = false;
-  ctx->split_valid = false;
-  ctx->eager_nch = 0;
-  ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = false;
-  ctx->stat_np = -1;
-  if (!m) { ctx->err = "pmx_upload_background: null mesh"; return 0; }
-  hipSetDevice(ctx->device);
-  if (!check_background(ctx, m, nsol, sols, imet)) return 0;
-  const int64_t np = m->np, ne = m->ne, nt = m->nt;
-  const bool dev_adja = m->adja == nullptr;   // no MMG3D_hashTetra on the host: device face matching
-  ctx->compact_recs = env_compact_records();
-  ctx->sample_mode = env_sample_mode();
-  ctx->bg_btv = false;
-  // the host packs the every-4th-tet hint sample with the tet records (the
-  // device-adjacency path: k_build_tetrec writes it)
-  const bool host_sample = !dev_adja && ctx->sample_mode == 0;
-  // a residency build of the next background's records shares the adjacency
-  // scratch: let it finish (its result, in the *_next buffers, is kept)
-  if (ctx->next_topo) CK(hipStreamSynchronize(ctx->topo));
-  Trace tr("background");
-  SolDesc sd{};
-  sd.nsol = nsol;
-  sd.imet = imet;
-  int S = 0;
-  for (int s = 0; s < nsol; s++) {
-    sd.size[s] = sols[s].size;
-    sd.off[s] = S;
-    S += sols[s].size;
-  }
-  sd.S = S;
-  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
-  const size_t hs_n = (size_t)(np + 1) * std::max(S, 1);
-  // pinned staging: xyz | tets (TetRec, or int4 when the device builds the
-  // adjacency) | packed hint sample | solutions; each part goes down as soon
-  // as it is packed (the tets in chunks), one sync at the end
-  const size_t trec = dev_adja ? sizeof(int4) : sizeof(TetRec);
-  const size_t o_p = 0, o_t = o_p + pmx_call::al256((size_t)(np + 1) * 24),
-               o_h = o_t + pmx_call::al256((size_t)(ne + 1) * trec),
-               o_s = o_h + pmx_call::al256(host_sample ? (size_t)ns * sizeof(int4) : 0),
-               total = o_s + pmx_call::al256(hs_n * sizeof(double));
-  CK(hipStreamSynchronize(ctx->stream));   // the arena may still feed an earlier copy
-  char *stg = pmx_hstage(ctx, total);
-  if (!stg) return 0;
-  // any return after the topology fork first waits for that stream (a later
-  // call may regrow the buffers its kernels use)
-  struct StreamGuard {
-    hipStream_t s = nullptr;
-    ~StreamGuard() { if (s) hipStreamSynchronize(s); }
-  } topo_guard;
-  if (!pmx_dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) || !pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) ||
-      (ctx->compact_recs && !pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !pmx_dgrow(ctx, ctx->d_wfar, 8) ||
-      !pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) || !pmx_dgrow(ctx, ctx->d_sol, hs_n) ||
-      !pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) || !pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) ||
-      !pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) ||
-      (dev_adja && (!pmx_dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) || !pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)))))
-    return 0;
-  hipStream_t st = ctx->stream;
-
-  // points -> dense xyz (24 B), bounding box per chunk
-  double *hp = (double *)(stg + o_p);
-  hp[0] = hp[1] = hp[2] = 0.0;
-  const char *pc = (const char *)m->point_c;
-  double blo[64][3], bhi[64][3];
-  const int nch = par_chunks(1, np + 1, [&](int c, int64_t i0, int64_t i1) {
-    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (int64_t i = i0; i < i1; i++) {
-      const double *cc = (const double *)(pc + i * m->point_stride);
-      for (int a = 0; a < 3; a++) {
-        hp[3 * i + a] = cc[a];
-        lo[a] = std::min(lo[a], cc[a]);
-        hi[a] = std::max(hi[a], cc[a]);
-      }
-    }
-    for (int a = 0; a < 3; a++) { blo[c][a] = lo[a]; bhi[c][a] = hi[a]; }
-  });
-  double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-  for (int c = 0; c < nch; c++)
-    for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], blo[c][a]); hi[a] = std::max(hi[a], bhi[c][a]); }
-  CK(hipMemcpyAsync(ctx->d_xyz.p, hp, (size_t)(np + 1) * 24, hipMemcpyHostToDevice, st));
-  tr.mark("points");
-  // tets -> TetRec with neighbour tet index (or the bare connectivity), + the
-  // packed hint sample (the connectivity of every PMX_HINT_STRIDE-th tet,
-  // contiguous: the hint build streams ne/4 * 16 B instead of touching every
-  // line of the tet records); in chunks, each DMA'd while the next is packed
-  TetRec *ht = (TetRec *)(stg + o_t);
-  int4 *htv = (int4 *)(stg + o_t);
-  int4 *hh = (int4 *)(stg + o_h);
-  if (dev_adja) htv[0] = make_int4(0, 0, 0, 0);
-  else memset(&ht[0], 0, sizeof(TetRec));
-  const char *tc = (const char *)m->tetra_v;
-  const int *adja_in = m->adja;
-  bool bad = false;
-  const int64_t ntc = std::max<int64_t>(1, std::min<int64_t>(8, ne >> 20));
-  for (int64_t c = 0; c < ntc; c++) {
-    const int64_t klo = (c == 0) ? 0 : 1 + ne * c / ntc, khi = 1 + ne * (c + 1) / ntc;
-    par_for(std::max<int64_t>(klo, 1), khi, [&](int64_t k0, int64_t k1) {
-      bool b = false;
-      for (int64_t k = k0; k < k1; k++) {
-        const int *v = (const int *)(tc + k * m->tetra_stride);
-        // indices the kernels will gather through: a valid tet (v[0] > 0,
-        // MG_EOK) must name vertices 1..np and neighbours 0..ne
-        const bool valid = v[0] > 0;
-        if (dev_adja) {
-          if (!valid) { st4(&htv[k], 0, 0, 0, 0); }
-          else {
-            for (int l = 0; l < 4; l++)
-              if (v[l] < 1 || v[l] > np) b = true;
-            st4(&htv[k], v[0], v[1], v[2], v[3]);
-          }
-        } else {
-          TetRec &r = ht[(size_t)k];
-          for (int l = 0; l < 4; l++) {
-            r.v[l] = v[l];
-            const int a = adja_in[4 * (k - 1) + 1 + l];
-            r.nb[l] = a / 4;
-            if (valid && (v[l] < 1 || v[l] > np || a < 0 || a / 4 > ne)) b = true;
-          }
-        }
-        if (host_sample && (k - 1) % PMX_HINT_STRIDE == 0)
-          hh[(k - 1) / PMX_HINT_STRIDE] = make_int4(v[0], v[1], v[2], v[3]);
-      }
-      if (b) __atomic_store_n(&bad, true, __ATOMIC_RELAXED);
-      std::atomic_thread_fence(std::memory_order_seq_cst);
-    });
-    if (bad) break;
-    if (dev_adja)
-      CK(hipMemcpyAsync(ctx->d_btv.p + klo, htv + klo, (size_t)(khi - klo) * sizeof(int4), hipMemcpyHostToDevice, st));
-    else
-      CK(hipMemcpyAsync(ctx->d_tets.p + klo, ht + klo, (size_t)(khi - klo) * sizeof(TetRec), hipMemcpyHostToDevice,
-                        st));
-  }
-  if (bad) {
-    ctx->err = "pmx_upload_background: tet vertex or adjacency index out of range";
-    return 0;
-  }
-  ctx->h_nbad.p[2] = 0;                        // no far fields unless compact records are built
-  if (!dev_adja) {
-    if (host_sample)
-      CK(hipMemcpyAsync(ctx->d_tets_s.p, hh, (size_t)ns * sizeof(int4), hipMemcpyHostToDevice, st));
-    if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, st);
-    // the owner sample (mode 2) while the host packs the solutions and trias
-    if (!ctx->order_hint_samples(ne, np, st)) return 0;
-  }
-  if (dev_adja) {
-    // face matching on the device (pmx_topo.hip), then the tet records and
-    // the hint sample from the device connectivity -- on the topology stream
-    // as soon as the connectivity is down, overlapping the solutions' and
-    // trias' packing and DMA; joined before the final sync
-    CK(hipEventRecord(ctx->ev_fork, st));
-    CK(hipStreamWaitEvent(ctx->topo, ctx->ev_fork, 0));
-    topo_guard.s = ctx->topo;
-    ctx->h_nbad.p[1] = 0;                      // [0] belongs to a pending residency build
-    if (!pmx_ctx_build_adja_device(ctx, ctx->d_btv.p, ne, np, ctx->d_adja.p, ctx->topo, ctx->h_nbad.p + 1))
-      return 0;
-    launch_build_tetrec(ctx->d_btv.p, ctx->d_adja.p, ne, PMX_HINT_STRIDE, ctx->d_tets.p, ctx->d_tets_s.p,
-                        ctx->topo);
-    if (ctx->compact_recs)
-      launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, ctx->topo);
-    if (!ctx->order_hint_samples(ne, np, ctx->topo)) return 0;
-    CK(hipEventRecord(ctx->ev_join, ctx->topo));
-  }
-  tr.mark("tets");
-  // solutions -> interleaved [np+1][S], in blocks of 1024 rows (each row's
-  // line written while it is in cache, not once per solution) and chunks
-  // whose DMA overlaps the packing of the next
-  double *hs = (double *)(stg + o_s);
-  // row 0: Mmg's unused slot, as the caller holds it (no kernel reads a
-  // vertex 0 -- but PMMG_prilen's parallel edges with a tensor metric and
-  // metRidTyp = 1 read met->m[ip] flat, src/quality_pmmg.c:466, i.e. row 0
-  // for ip < 6)
-  memset(hs, 0, (size_t)std::max(S, 1) * sizeof(double));
-  for (int s = 0; s < nsol; s++)
-    for (int j = 0; j < sols[s].size; j++) hs[sd.off[s] + j] = sols[s].m[j];
-  if (S == 0) {
-    memset(hs, 0, hs_n * sizeof(double));
-    CK(hipMemcpyAsync(ctx->d_sol.p, hs, hs_n * sizeof(double), hipMemcpyHostToDevice, st));
-  } else {
-    const int64_t nsc = std::max<int64_t>(1, std::min<int64_t>(4, (np * S) >> 21));
-    for (int64_t c = 0; c < nsc; c++) {
-      const int64_t r0 = (c == 0) ? 0 : 1 + np * c / nsc, r1 = 1 + np * (c + 1) / nsc;
-      par_for(std::max<int64_t>(r0, 1), r1, [&](int64_t i0, int64_t i1) {
-        for (int64_t b0 = i0; b0 < i1; b0 += 1024) {
-          const int64_t b1 = std::min(i1, b0 + 1024);
-          for (int s = 0; s < nsol; s++) {
-            const int sz = sols[s].size, off = sd.off[s];
-            const double *src = sols[s].m;
-            for (int64_t i = b0; i < b1; i++)
-              for (int j = 0; j < sz; j++) hs[(size_t)i * S + off + j] = src[i * sz + j];
-          }
-        }
-      });
-      CK(hipMemcpyAsync(ctx->d_sol.p + r0 * S, hs + r0 * S, (size_t)((r1 - r0) * S) * sizeof(double),
-                        hipMemcpyHostToDevice, st));
-    }
-  }
-  tr.mark("solutions");
-  // boundary triangles
-  std::vector<TriRec> htr;
-  if (!stage_trias(ctx, m, np, htr)) return 0;
-  ctx->np = np; ctx->ne = ne; ctx->nt = nt; ctx->hausd = m->hausd;
-  ctx->sd = sd;
-  if (!setup_grids(ctx, lo, hi, ne)) return 0;
-  CK(hipMemcpyAsync(ctx->d_tris.p, htr.data(), htr.size() * sizeof(TriRec), hipMemcpyHostToDevice, st));
-  if (!ctx->check_fans(st)) return 0;
-  // the node -> trias fans are the step's (pmx_run: PMMG_precompute_nodeTrias
-  // runs inside the reference's call)
-  if (dev_adja) CK(hipStreamWaitEvent(st, ctx->ev_join, 0));
-  CK(hipGetLastError());
-  tr.mark("trias + topology");
-  CK(hipStreamSynchronize(ctx->stream));   // host staging vectors die here
-  tr.mark("sync");
-  if (dev_adja && ctx->h_nbad.p[1]) {
-    ctx->err = "pmx_upload_background: non-manifold tet faces";
-    return 0;
-  }
-  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad.p[4] == 0;
-  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[5] : 0;
-  ctx->bg_btv = dev_adja;
-  ctx->have_bg = true;
   return 1;
 }
 
@@ -945,17 +571,8 @@ bool pmx_ctx::pack_new_tets() {
   // the device) on the topo stream, after the tets' DMA, while the step and
   // the download go on
   if (residency && ntet > 0) {
-    const int64_t ns = (ntet + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
-    if (!pmx_dgrow(this, d_adja, (size_t)(4 * ntet + 5)) || !pmx_dgrow(this, d_tets_next, (size_t)(ntet + 1)) ||
-        (compact_recs && !pmx_dgrow(this, d_wrec_next, (size_t)(ntet + 1))) || !pmx_dgrow(this, d_wfar, 8) ||
-        !pmx_dgrow(this, d_tets_s_next, (size_t)std::max<int64_t>(ns, 1)))
-      return false;
-    *h_nbad.p = 0;
     CK(hipStreamWaitEvent(topo, ev_tets, 0));
-    if (!pmx_ctx_build_adja_device(this, d_ntetv.p, ntet, n, d_adja.p, topo, h_nbad.p)) return false;
-    launch_build_tetrec(d_ntetv.p, d_adja.p, ntet, PMX_HINT_STRIDE, d_tets_next.p, d_tets_s_next.p, topo);
-    h_nbad.p[3] = 0;
-    if (compact_recs) launch_build_wrec(d_tets_next.p, ntet, d_wrec_next.p, d_wfar.p + 1, h_nbad.p + 3, topo);
+    if (!build_records(d_ntetv.p, nullptr, ntet, n, records_next(), topo)) return false;
     CK(hipEventRecord(ev_topo, topo));
     next_topo = true;
   }
@@ -982,49 +599,6 @@ bool pmx_ctx::fix_orphans() {
   if (tets_inflight) CK(hipStreamWaitEvent(stream, ev_tets, 0));   // the marks are written on `up`
   OrphanRows r{d_wmask.p, d_elem.p, d_status.p, d_steps.p, d_start.p, d_edge.p, d_vertex.p, d_kind.p};
   launch_orphans(d_qmark.p, nq, (uint8_t)last_const_bit, r, stream);
-  CK(hipGetLastError());
-  return true;
-}
-
-// The hint sample, once the tets are on the device and np set
-// (sample_mode, PMX_HINT_SAMPLE_ORDER at the upload): 0 every 4th tet in tet
-// order, packed with the tet records (nothing to do here); 2 one tet per
-// vertex, in vertex order (k_vmin_owner; its count lands in h_nbad[5], nsamp
-// after the upload's sync) -- A/Bs in DESIGN.md section 7 r05 / r06.  (r05's
-// mode 1, the every-4th-tet sample sorted by smallest vertex, was dropped in
-// r06: its sort could not be redone by a FRESH step.)
-bool pmx_ctx::order_hint_samples(int64_t ne, int64_t np, hipStream_t s) {
-  samples_sorted = samples_owner = false;
-  if (sample_mode != 2 || np < 1 || ne < 1) return true;
-  const size_t tb = owner_scan_temp_bytes(np);
-  if (!pmx_dgrow(this, d_skey, (size_t)(np + 2)) || !pmx_dgrow(this, d_sidx, (size_t)(2 * (np + 1))) ||
-      !pmx_dgrow(this, d_salt, (size_t)(np + 1)) || !pmx_dgrow(this, d_tets_sk, (size_t)(np + 1)) ||
-      !pmx_dgrow(this, d_stmp, std::max<size_t>(tb, 1)) || !pmx_dgrow(this, d_wfar, 8))
-    return false;
-  if (!launch_owner_sample(d_tets.p, ne, np, d_skey.p, d_sidx.p, d_sidx.p + (np + 1), d_salt.p, d_tets_sk.p,
-                           d_wfar.p + 4, h_nbad.p + 5, d_stmp.p, tb, s)) {
-    err = "hint sample: vertex owners";
-    return false;
-  }
-  std::swap(d_tets_s, d_salt);
-  samples_sorted = samples_owner = true;
-  return true;
-}
-
-// PMX_RUN_FRESH_BACKGROUND: the device passes an upload runs on the raw
-// arrays, again, in stream order on s -- a ParMmg iteration brings a new
-// background (PMMG_update_oldGrps, src/libparmmg1.c:653) and the reference
-// recomputes its derived data inside the call (src/interpmesh_pmmg.c:514-518)
-bool pmx_ctx::rederive(hipStream_t s) {
-  pmx_ctx *ctx = this;                     // CK()
-  if (bg_btv) {
-    // face matching of the uploaded connectivity, then the tet records and
-    // the every-4th-tet sample (MMG3D_hashTetra's adjacency on the device)
-    if (!pmx_ctx_build_adja_device(this, d_btv.p, ne, np, d_adja.p, s, h_nbad.p + 1)) return false;
-    launch_build_tetrec(d_btv.p, d_adja.p, ne, PMX_HINT_STRIDE, d_tets.p, d_tets_s.p, s);
-  }
-  if (compact_recs) launch_build_wrec(d_tets.p, ne, d_wrec.p, d_wfar.p, h_nbad.p + 2, s);
-  if (sample_mode == 2 && !order_hint_samples(ne, np, s)) return false;
   CK(hipGetLastError());
   return true;
 }
@@ -1064,9 +638,9 @@ static void fill_vol_args(pmx_ctx *ctx, const SolDesc &sd, const pmx_run_opts &o
   // faster; 9 %, 32-B 1.5 % faster; appended 41 %, 32-B 5.5 % faster --
   // DESIGN.md section 7).  exp 18: compact records always
   if (!ctx->compact_recs ||
-      (A.exp != 18 && (uint64_t)ctx->h_nbad.p[2] * PMX_WREC_FAR_DIV > (uint64_t)std::max<int64_t>(ctx->ne, 1)))
+      (A.exp != 18 && (uint64_t)ctx->h_nbad.p[PMX_H_FAR] * PMX_WREC_FAR_DIV > (uint64_t)std::max<int64_t>(ctx->ne, 1)))
     A.wrec = nullptr;
-  A.far = ctx->h_nbad.p[2] > 0 ? 1 : 0;
+  A.far = ctx->h_nbad.p[PMX_H_FAR] > 0 ? 1 : 0;
   // point-map starts: no grid; the walks' PM instantiations read the start
   // elements the classification resolved, passed in its place
   if (opts.flags & PMX_RUN_POINTMAP) A.grid = ctx->d_pstart.p;
@@ -1813,172 +1387,6 @@ int pmx_upload_new_tets(pmx_ctx *ctx, const int *tetra_v, int64_t tetra_stride, 
   return 1;
 }
 
-int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const pmx_sol_view *sols) {
-  if (!ctx) return 0;
-  if (!m) { ctx->err = "pmx_promote_background: null mesh"; return 0; }
-  if (!ctx->ran || !ctx->have_pts || ctx->out_n != ctx->nq || ctx->out_S != ctx->sd.S) {
-    ctx->err = "pmx_promote_background: no step has run on the current uploads";
-    return 0;
-  }
-  if (!ctx->have_ntet) { ctx->err = "pmx_promote_background: upload the new tets first"; return 0; }
-  if (ctx->pts_first != 1) {
-    ctx->err = "pmx_promote_background: the points view must start at 1 (Mmg numbering)";
-    return 0;
-  }
-  const int64_t n = ctx->nq, ne = ctx->n_ntet, nt = m->nt;
-  if (m->np != n || m->ne != ne || n < 1) {
-    ctx->err = "pmx_promote_background: mesh sizes differ from the uploaded points / new tets";
-    return 0;
-  }
-  if (nt < 0 || (nt > 0 && (!m->tria_v || !m->adjt || m->tria_stride < 12))) {
-    ctx->err = "pmx_promote_background: nt > 0 requires tria_v and adjt";
-    return 0;
-  }
-  const SolDesc sd = ctx->sd;
-  if (nsol != sd.nsol || (nsol > 0 && !sols)) {
-    ctx->err = "pmx_promote_background: solution list differs from the step's";
-    return 0;
-  }
-  for (int s = 0; s < nsol; s++)
-    if (sols[s].size != sd.size[s]) {
-      ctx->err = "pmx_promote_background: solution size differs from the step's";
-      return 0;
-    }
-  if (m->adja) {
-    // the walks gather through these: every neighbour of a valid tet must
-    // name a face of 1..ne (as pmx_upload_background checks)
-    bool badj = false;
-    par_chunks(1, ne + 1, [&](int, int64_t k0, int64_t k1) {
-      bool b = false;
-      for (int64_t k = k0; k < k1 && !b; k++) {
-        if (m->tetra_v && *(const int *)((const char *)m->tetra_v + k * m->tetra_stride) <= 0) continue;
-        for (int f = 0; f < 4; f++) {
-          const int a = m->adja[4 * (k - 1) + 1 + f];
-          if (a < 0 || a / 4 > ne) b = true;
-        }
-      }
-      if (b) __atomic_store_n(&badj, true, __ATOMIC_RELAXED);
-    });
-    if (badj) { ctx->err = "pmx_promote_background: adjacency entry out of range"; return 0; }
-  }
-  hipSetDevice(ctx->device);
-  Trace tr("promote");
-  hipStream_t st = ctx->stream;
-  if (!ctx->fix_orphans() || !ctx->ensure_tets(st)) return 0;
-  CK(hipStreamSynchronize(st));
-  if (!ctx->check_device_errors()) return 0;
-  tr.mark("sync");
-  const int S = sd.S;
-  // rows the step did not write keep the caller's values (Mmg's own, or the
-  // frozen-point copy): which ones, from the write masks
-  char *stg = pmx_hstage(ctx, (size_t)n);
-  if (!stg) return 0;
-  CK(hipMemcpyAsync(stg, ctx->d_wmask.p, (size_t)n, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  const uint8_t *wm = (const uint8_t *)stg;
-  const unsigned full = (1u << nsol) - 1u;
-  // per chunk, then concatenated in chunk order
-  std::vector<std::vector<int4>> cent(64);
-  std::vector<std::vector<double>> cval(64);
-  bool missing = false;
-  const int nch = par_chunks(0, n, [&](int c, int64_t j0, int64_t j1) {
-    for (int64_t j = j0; j < j1; j++) {
-      if ((wm[j] & full) == full) continue;      // every solution written (the common case)
-      for (int s = 0; s < nsol; s++) {
-        if (wm[j] & (1u << s)) continue;
-        const int sz = sd.size[s];
-        if (!sols[s].m) { __atomic_store_n(&missing, true, __ATOMIC_RELAXED); continue; }
-        cent[(size_t)c].push_back(make_int4((int)(j + 1), sd.off[s], sz, 0));
-        const double *src = sols[s].m + j * sz;   // pmx_download's layout
-        for (int q = 0; q < 6; q++) cval[(size_t)c].push_back(q < sz ? src[q] : 0.0);
-      }
-    }
-  });
-  if (missing) {
-    ctx->err = "pmx_promote_background: a row the step did not write needs the caller's solution";
-    return 0;
-  }
-  std::vector<int4> ent;
-  std::vector<double> vals;
-  for (int c = 0; c < nch; c++) {
-    ent.insert(ent.end(), cent[(size_t)c].begin(), cent[(size_t)c].end());
-    vals.insert(vals.end(), cval[(size_t)c].begin(), cval[(size_t)c].end());
-  }
-  tr.mark("unwritten rows");
-  // boundary trias of the new mesh (the host's: Mmg's numbering)
-  std::vector<TriRec> htr;
-  if (!stage_trias(ctx, m, n, htr)) return 0;
-  tr.mark("trias");
-  // the background invalid until this completes
-  ctx->have_bg = ctx->have_derived = ctx->have_tetv = ctx->have_qual = ctx->have_ptag = ctx->have_csr = ctx->have_surf = false;
-  ctx->have_pmap = false;
-  ctx->split_valid = false;
-  ctx->bg_btv = false;                     // records from the new tets (or the caller's adja), not d_btv
-  ctx->stat_np = -1;
-  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
-  if (!pmx_dgrow(ctx, ctx->d_xyz, (size_t)(n + 1) * 3) || !pmx_dgrow(ctx, ctx->d_sol, (size_t)(n + 1) * std::max(S, 1)) ||
-      !pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) || !pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) ||
-      !pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)) || !pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) ||
-      !pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) || !pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(n + 1)))
-    return 0;
-  const bool tags = ctx->have_qtag;
-  if (tags && !pmx_dgrow(ctx, ctx->d_ptag, (size_t)(n + 1))) return 0;
-  launch_promote(ctx->d_qxyz.p, ctx->d_out.p, tags ? ctx->d_qtag.p : nullptr, n, S, ctx->d_xyz.p, ctx->d_sol.p,
-                 tags ? ctx->d_ptag.p : nullptr, st);
-  if (!ent.empty()) {
-    if (!pmx_dgrow(ctx, ctx->d_pent, ent.size()) || !pmx_dgrow(ctx, ctx->d_pval, vals.size())) return 0;
-    CK(hipMemcpyAsync(ctx->d_pent.p, ent.data(), ent.size() * sizeof(int4), hipMemcpyHostToDevice, st));
-    CK(hipMemcpyAsync(ctx->d_pval.p, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    launch_patch_rows(ctx->d_pent.p, ctx->d_pval.p, (int64_t)ent.size(), S, ctx->d_sol.p, st);
-  }
-  // tet records: prepared while the step ran (residency on), else from the
-  // caller's Mmg adjacency (mesh->adja after remeshing) or one built here
-  tr.mark("promote launch");
-  const bool prepared = ctx->next_topo;
-  if (prepared) {                          // the residency build shares d_adja: wait for it
-    CK(hipEventSynchronize(ctx->ev_topo));
-    tr.mark("wait topo");
-    ctx->next_topo = false;
-  }
-  if (prepared && !m->adja) {
-    if (*ctx->h_nbad.p) { ctx->err = "pmx_promote_background: non-manifold tet faces"; return 0; }
-    std::swap(ctx->d_tets, ctx->d_tets_next);
-    std::swap(ctx->d_wrec, ctx->d_wrec_next);
-    ctx->h_nbad.p[2] = ctx->h_nbad.p[3];
-    std::swap(ctx->d_tets_s, ctx->d_tets_s_next);
-  } else {
-    if (m->adja) {
-      CK(hipMemcpyAsync(ctx->d_adja.p, m->adja, (size_t)(4 * ne + 5) * sizeof(int), hipMemcpyHostToDevice, st));
-    } else if (!pmx_ctx_build_adja_device(ctx, ctx->d_ntetv.p, ne, n, ctx->d_adja.p, st, nullptr)) {
-      return 0;
-    }
-    if ((ctx->compact_recs && !pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !pmx_dgrow(ctx, ctx->d_wfar, 8)) return 0;
-    launch_build_tetrec(ctx->d_ntetv.p, ctx->d_adja.p, ne, PMX_HINT_STRIDE, ctx->d_tets.p, ctx->d_tets_s.p, st);
-    ctx->h_nbad.p[2] = 0;
-    if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, st);
-  }
-  ctx->np = n;
-  ctx->ne = ne;
-  ctx->nt = nt;
-  ctx->hausd = m->hausd;
-  tr.mark("tet records");
-  if (!setup_grids(ctx, ctx->qlo, ctx->qhi, ne)) return 0;
-  if (!ctx->order_hint_samples(ne, ctx->np, st)) return 0;
-  tr.mark("grids");
-  CK(hipMemcpyAsync(ctx->d_tris.p, htr.data(), htr.size() * sizeof(TriRec), hipMemcpyHostToDevice, st));
-  if (!ctx->check_fans(st)) return 0;
-  CK(hipGetLastError());
-  CK(hipStreamSynchronize(st));            // host vectors die here
-  ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad.p[4] == 0;
-  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[5] : 0;
-  tr.mark("uploads + sync");
-  ctx->have_ptag = tags;
-  // the points and the results were consumed: the next step needs new points
-  ctx->have_pts = ctx->ran = ctx->have_ntet = false;
-  ctx->have_bg = true;
-  return 1;
-}
-
 }  // extern "C"
 
 // ---- pmx_ctx members ----------------------------------------------------------
@@ -2019,55 +1427,3 @@ pmx_ctx::~pmx_ctx() {
   pmx_split_free(this);
   pmx_merge_free(this);
 }
-
-// ---- a device-resident group as the background (pmx_merge_adopt) ----------------
-
-// pmx_upload_background's device-adjacency path with nt = 0, its host packing
-// and DMA replaced by device-to-device copies
-bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
-                         const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]) {
-  const pmx_call call{ctx, who, ctx->stream};
-  ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
-  ctx->have_pmap = false;
-  ctx->split_valid = false;
-  ctx->eager_nch = 0;
-  ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = false;
-  ctx->stat_np = -1;
-  if (np < 1 || ne < 1 || np >= (1LL << 31) - 1 || 4 * ne >= (1LL << 31)) return call.fail("mesh sizes out of range");
-  ctx->compact_recs = env_compact_records();
-  ctx->sample_mode = env_sample_mode();
-  ctx->bg_btv = false;
-  if (ctx->next_topo && !call.hip(hipStreamSynchronize(ctx->topo), "residency build")) return false;
-  const int S = sd.S;
-  const int64_t ns = (ne + PMX_HINT_STRIDE - 1) / PMX_HINT_STRIDE;
-  const size_t hs_n = (size_t)(np + 1) * std::max(S, 1);
-  if (!pmx_dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) || !pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) ||
-      (ctx->compact_recs && !pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) || !pmx_dgrow(ctx, ctx->d_wfar, 8) ||
-      !pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) || !pmx_dgrow(ctx, ctx->d_sol, hs_n) ||
-      !pmx_dgrow(ctx, ctx->d_tris, 1) || !pmx_dgrow(ctx, ctx->d_trn, 1) ||
-      !pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) || !pmx_dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) ||
-      !pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5)))
-    return false;
-  hipStream_t st = ctx->stream;
-  if (!call.hip(hipMemcpyAsync(ctx->d_xyz.p, xyz, (size_t)(np + 1) * 24, hipMemcpyDeviceToDevice, st), "points") ||
-      !call.hip(hipMemcpyAsync(ctx->d_btv.p, tv, (size_t)(ne + 1) * sizeof(int4), hipMemcpyDeviceToDevice, st), "tets") ||
-      !call.hip(S > 0 ? hipMemcpyAsync(ctx->d_sol.p, sol, hs_n * sizeof(double), hipMemcpyDeviceToDevice, st)
-                      : hipMemsetAsync(ctx->d_sol.p, 0, hs_n * sizeof(double), st), "solutions") ||
-      !call.hip(hipMemsetAsync(ctx->d_tris.p, 0, sizeof(TriRec), st), "trias"))
-    return false;
-  ctx->h_nbad.p[1] = ctx->h_nbad.p[2] = 0;
-  if (!pmx_ctx_build_adja_device(ctx, ctx->d_btv.p, ne, np, ctx->d_adja.p, st, ctx->h_nbad.p + 1)) return false;
-  launch_build_tetrec(ctx->d_btv.p, ctx->d_adja.p, ne, PMX_HINT_STRIDE, ctx->d_tets.p, ctx->d_tets_s.p, st);
-  if (ctx->compact_recs) launch_build_wrec(ctx->d_tets.p, ne, ctx->d_wrec.p, ctx->d_wfar.p, ctx->h_nbad.p + 2, st);
-  if (!ctx->order_hint_samples(ne, np, st)) return false;
-  ctx->np = np; ctx->ne = ne; ctx->nt = 0; ctx->hausd = 0.0;
-  ctx->sd = sd;
-  if (!setup_grids(ctx, lo, hi, ne) || !ctx->check_fans(st)) return false;
-  if (!call.hip(hipGetLastError(), "launch") || !call.hip(hipStreamSynchronize(st), "sync")) return false;
-  if (ctx->h_nbad.p[1]) return call.fail("non-manifold tet faces");
-  ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[5] : 0;
-  ctx->bg_btv = true;
-  ctx->have_bg = true;
-  return true;
-}
-

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <string>
 #include <vector>
@@ -17,6 +20,37 @@
 // the walk takes the 32-B tet records instead of the compact ones when more
 // than 1/PMX_WREC_FAR_DIV of the tets have a far neighbour field (pmx_wrec.h)
 #define PMX_WREC_FAR_DIV 16
+
+// Slots of pmx_ctx::h_nbad (pinned words the device writes in stream order,
+// valid on the host after a sync of that stream) and of pmx_ctx::d_wfar (their
+// device counters).  "next" is the residency build's record set.
+enum {
+  PMX_H_NONMANIFOLD_NEXT = 0,   // non-manifold tet faces of the next record set's face matching
+  PMX_H_NONMANIFOLD = 1,        // ... of the current one's (upload, adopt, promote, FRESH step)
+  PMX_H_FAR = 2,                // tets of d_wrec with a far neighbour field (pmx_wrec.h)
+  PMX_H_FAR_NEXT = 3,           // ... of d_wrec_next
+  PMX_H_BAD_FANS = 4,           // check_fans: vertices whose fan the rotation cannot build
+  PMX_H_NSAMP = 5,              // entries of the vertex-owner hint sample
+  PMX_H_WORDS = 8
+};
+enum {
+  PMX_D_FAR = 0,                // far-field counter of d_wrec
+  PMX_D_FAR_NEXT = 1,           // ... of d_wrec_next
+  PMX_D_FANS_STEP = 2,          // bad fans of the step's rotation
+  PMX_D_FANS_CHECK = 3,         // ... of the upload's check
+  PMX_D_NSAMP = 4,              // owner-sample count
+  PMX_D_WORDS = 8
+};
+
+// Where build_records puts a background's tet records: the buffers, the
+// d_wfar slot of the compact records' far counter and the h_nbad slots of the
+// non-manifold and far counts (pmx_ctx::records_current / records_next)
+struct RecordSet {
+  DevBuf<TetRec> *tets;
+  DevBuf<WRec> *wrec;
+  DevBuf<int4> *sample;
+  int d_far, h_nonmanifold, h_far;
+};
 
 struct pmx_ctx {
   int device = 0;
@@ -47,7 +81,7 @@ struct pmx_ctx {
   DevBuf<double> d_xyz;                 // old vertices, x y z (24 B), slot 0 unused
   DevBuf<TetRec> d_tets;
   DevBuf<WRec> d_wrec;                  // the walk's compact copy of d_tets (built with it)
-  DevBuf<unsigned> d_wfar;              // [0] / [1] far-field counters of d_wrec / d_wrec_next, [2] / [3] bad fans (step / upload check), [4] owner-sample count
+  DevBuf<unsigned> d_wfar;              // device counters, PMX_D_WORDS of them: the PMX_D_* slots above
   DevBuf<double> d_sol;
   DevBuf<int4> d_tets_s;                // hint sample: every 4th tet (default, packed with the tets) or one owner tet per vertex (order_hint_samples)
   DevBuf<int> d_tets_sk;                // its tet indices (samples_sorted)
@@ -214,8 +248,13 @@ struct pmx_ctx {
   bool have_ntet = false;               //   vertex = points-view index - first + 1
   int64_t n_ntet = 0;
   double qlo[3]{}, qhi[3]{};            // bbox of the uploaded new points
-  // device adjacency of promoted backgrounds (pmx_topo.hip), reused buffers
+  // device adjacency (pmx_topo.hip), reused buffers.  d_adja and the face
+  // matching's scratch below are build_records' alone: one scratch shared by
+  // the builds on the main and the topo stream, kept in order by ev_adja
+  // (waited for before a build's first write, recorded after its last read;
+  // created by the first build)
   DevBuf<int> d_adja;
+  DevEvent ev_adja;
   DevBuf<int4> d_btv;                   // background connectivity when its adjacency is built here
   DevBuf<unsigned> d_tcnt, d_toff, d_tbad;
   DevBuf<int4> d_trec;
@@ -231,9 +270,7 @@ struct pmx_ctx {
   DevBuf<TetRec> d_tets_next;
   DevBuf<WRec> d_wrec_next;
   DevBuf<int4> d_tets_s_next;
-  // [2] / [3]: tets of d_wrec / d_wrec_next with a far neighbour field (pmx_wrec.h), [4]: bad fans,
-  // [5]: entries of the vertex-owner hint sample
-  PinBuf<unsigned> h_nbad;              // pinned [2]: non-manifold faces of that build, [1] of a background upload's
+  PinBuf<unsigned> h_nbad;              // pinned counts, PMX_H_WORDS of them: the PMX_H_* slots above
   DevBuf<double> d_nqual;
   bool have_qtag = false;               // raw tags of the new points
   DevBuf<uint16_t> d_qtag;
@@ -269,9 +306,24 @@ struct pmx_ctx {
   ~pmx_ctx();                           // the split plan (pmx_capi.hip); the members release themselves
   DevEvent *next_event_slot();          // nullptr + err on failure
   bool order_hint_samples(int64_t ne, int64_t nverts, hipStream_t s);
+  // the background's record set, and the one the residency build prepares
+  RecordSet records_current() { return {&d_tets, &d_wrec, &d_tets_s, PMX_D_FAR, PMX_H_NONMANIFOLD, PMX_H_FAR}; }
+  RecordSet records_next() {
+    return {&d_tets_next, &d_wrec_next, &d_tets_s_next, PMX_D_FAR_NEXT, PMX_H_NONMANIFOLD_NEXT, PMX_H_FAR_NEXT};
+  }
+  // Connectivity -> tet records on stream s (pmx_background.hip), the only
+  // code that touches d_adja: the face matching of tv (1-based int4 on the
+  // device, slot 0 unused) -- or, when the caller has Mmg's adjacency
+  // (host_adja, 4 ne + 5 ints), its copy to the device --, then the 32-B
+  // records with the every-4th-tet sample and, with compact_recs, the walk's
+  // records; tv == nullptr: the 32-B records are in place, only the walk's
+  // are built.  The destination buffers are grown; the counts land in dst's
+  // h_nbad slots when s gets there.
+  bool build_records(const int4 *tv, const int *host_adja, int64_t ne, int64_t np, const RecordSet &dst,
+                     hipStream_t s);
   // PMX_RUN_FRESH_BACKGROUND: the per-background device passes of an upload
   // (face matching + records when the device built the adjacency, compact
-  // records, owner sample), again on stream s (pmx_capi.hip)
+  // records, owner sample), again on stream s (pmx_background.hip)
   bool rederive(hipStream_t s);
   // the orphan marks of the new tets on stream s: d_qmark[j] = 1 when a valid
   // new tet holds point j (the reference's vertex loop, src/interpmesh_pmmg.c:535-541)
@@ -317,10 +369,56 @@ char *pmx_hstage(pmx_ctx *ctx, size_t bytes);
 bool pmx_download_qual(pmx_ctx *ctx, const double *dev, int64_t ne, double *qual, int64_t stride);
 // f(i0, i1) over [lo, hi) on the host pool (pmx_capi.hip)
 void pmx_par_for(int64_t lo, int64_t hi, const std::function<void(int64_t, int64_t)> &f);
+// the host pool itself (pmx_capi.hip): its thread count, the range size below
+// which a pass stays serial, job(0..n-1) over the workers and the caller
+unsigned pmx_host_threads();
+int64_t pmx_host_threads_min();
+void pmx_host_pool_run(const std::function<void(int)> &job, int n);
+// f(chunk, lo, hi) over C contiguous chunks of [lo, hi); returns C
+template <class F> static int par_chunks(int64_t lo, int64_t hi, F f) {
+  const int64_t n = hi - lo;
+  const int C = (pmx_host_threads() <= 1 || n < pmx_host_threads_min()) ? 1 : (int)pmx_host_threads();
+  if (C == 1) { f(0, lo, hi); return 1; }
+  const int64_t chunk = (n + C - 1) / C;
+  const std::function<void(int)> job = [&](int i) {
+    const int64_t a = lo + (int64_t)i * chunk, b = std::min(hi, a + chunk);
+    f(i, a, std::max(a, b));
+  };
+  pmx_host_pool_run(job, C);
+  return C;
+}
+template <class F> static void par_for(int64_t lo, int64_t hi, F f) {
+  par_chunks(lo, hi, [&](int, int64_t a, int64_t b) { if (a < b) f(a, b); });
+}
+// streaming (non-temporal) 16-B stores into the pinned staging: the host
+// never reads those lines again, and a plain store first reads each line for
+// ownership (a third of the packing traffic).  A pass ends with a full fence
+// before its DMA is issued.
+typedef int pmx_v4i __attribute__((ext_vector_type(4)));
+static inline void st4(int4 *p, int a, int b, int c, int d) {
+  const pmx_v4i v = {a, b, c, d};
+  __builtin_nontemporal_store(v, (pmx_v4i *)p);
+}
+// PMX_TRACE=1: host phase timings of the staging calls on stderr
+struct Trace {
+  const char *who;
+  bool on;
+  std::chrono::steady_clock::time_point t0, last;
+  explicit Trace(const char *w) : who(w), on(getenv("PMX_TRACE") != nullptr) {
+    if (on) t0 = last = std::chrono::steady_clock::now();
+  }
+  void mark(const char *what) {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[pmx] %s %-22s %8.3f ms\n", who, what,
+            std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+};
 
 // face adjacency of device connectivity (1-based int4, slot 0 unused) into
 // dadja (Mmg layout, 4 ne + 5 ints), context-owned scratch; false on a
-// non-manifold face or a failure (ctx->err)
+// non-manifold face or a failure (ctx->err).  Called by build_records only.
 // h_nbad != NULL: asynchronous on stream s, the non-manifold count lands in
 // *h_nbad (pinned) when the stream gets there; NULL: checked before returning
 bool pmx_ctx_build_adja_device(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t np, int *dadja,
@@ -346,7 +444,7 @@ void pmx_merge_free(pmx_ctx *ctx);
 // unused; xyz: 3 (np + 1) doubles; sol: (np + 1) max(S, 1) doubles, interleaved;
 // bounding box lo / hi) becomes the uploaded group, as pmx_upload_background
 // with adja = NULL and nt = 0 leaves it; the copies are device to device on
-// the context stream (pmx_capi.hip).  false + ctx->err, no background kept.
+// the context stream (pmx_background.hip).  false + ctx->err, no background kept.
 bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
                          const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]);
 // error of a call made without a context (pmx_last_error(NULL), per thread)

@@ -213,6 +213,55 @@ def test_failed_upload_leaves_no_usable_context(transfer):
     assert np.all(r.status != 0)
 
 
+@pytest.mark.parametrize("entry", ["upload", "promote", "adopt"])
+def test_failed_install_leaves_no_background(entry):
+    """Every way a mesh becomes the uploaded group invalidates the old one
+    first: an install that fails half way (a tet vertex > np in an upload;
+    three tets on one face in a promotion's new tets or in an adopted group)
+    leaves no background -- the next step, the qualities and a split refuse
+    instead of using stale sizes -- and a good upload makes the context usable
+    again.  (A promotion refused by its argument checks moves nothing:
+    test_promote_requires_step_and_tets.)"""
+    from parmmg_amd.transfer import Transfer
+    m, x, t, sols = cube_case(5, metric="iso")
+    # points inside the unit cube; tets 2 and 3 both repeat the face (1, 2, 3) of tet 1
+    xyz = np.array([[0, 0, 0], [.2, .2, .5], [.8, .2, .5], [.2, .8, .5], [.3, .3, .9], [.3, .3, .1], [.6, .6, .1]])
+    tv = np.array([[0, 0, 0, 0], [1, 2, 3, 4], [1, 3, 2, 5], [1, 3, 2, 6]], np.int32)
+    tr = Transfer(0)
+    try:
+        _run(tr, m, x, t, sols)
+        tr.tetra_qual(m.ne)                               # served while the background stands
+        if entry == "upload":
+            bad = M.Mesh(m.xyz, m.tet.copy(), m.adja, m.tria, m.adjt)
+            bad.tet[3, 2] = m.np + 5
+            with pytest.raises(RuntimeError, match="out of range"):
+                tr.upload_background(bad, sols, 0)
+        elif entry == "promote":
+            tets0 = tv - 1
+            tets0[0] = -1
+            tr.upload_points(xyz[1:], np.zeros(6, np.uint16), tets0)
+            tr.run()
+            r = tr.download(init=[np.zeros((6, s.shape[1])) for s in sols])
+            assert np.all(r.status != 0)
+            new = M.Mesh(xyz, tv, np.zeros(4 * 3 + 5, np.int32), np.zeros((1, 3), np.int32), np.zeros(4, np.int32))
+            with pytest.raises(RuntimeError, match="non-manifold tet faces"):
+                tr.promote_background(new, r.sols, adja=False)
+        else:
+            tr.merge_groups([{"tetra_v": tv, "xyz": xyz, "sols": [np.ones((7, s.shape[1])) for s in sols]}])
+            with pytest.raises(RuntimeError, match="non-manifold tet faces"):
+                tr.merge_adopt(0)
+        with pytest.raises(RuntimeError, match="upload background and points first"):
+            tr.run()
+        with pytest.raises(RuntimeError, match="upload a group first"):
+            tr.tetra_qual(m.ne)
+        with pytest.raises(RuntimeError, match="upload a group first"):
+            tr.split_groups(np.zeros(m.ne, np.int32), 1)
+        r = _run(tr, m, x, t, sols)
+        assert np.all(r.status != 0)
+    finally:
+        tr.close()
+
+
 def test_stale_results_refused_after_new_points(transfer):
     """results of a step are not downloadable once the points or
     the background changed (sizes would disagree)."""

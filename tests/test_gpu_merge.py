@@ -349,6 +349,29 @@ def test_adopt_equals_upload(transfer, name):
         transfer.merge_release()
 
 
+def test_adopt_then_fresh_step(transfer):
+    """A FRESH step on an adopted group matches its faces and builds its tet
+    records again from the connectivity the adopt kept: same bytes as the
+    default step before it and after it."""
+    _, groups, comm = split_of("k6_slabs8")
+    transfer.merge_groups(groups, comm)
+    try:
+        transfer.merge_adopt(0)
+        pts = np.random.default_rng(7).uniform(0.05, 0.95, (300, 3))
+        transfer.upload_points(pts, np.zeros(len(pts), np.uint16))
+        res = []
+        for flags in (0, N.RUN_FRESH_BACKGROUND, 0):
+            transfer.run(flags=flags)
+            res.append(transfer.download())
+        assert np.all(res[0].status != 0)
+        for r in res[1:]:
+            assert np.array_equal(r.elem, res[0].elem) and np.array_equal(r.status, res[0].status)
+            for x, y in zip(r.sols, res[0].sols):
+                assert x.tobytes() == y.tobytes()
+    finally:
+        transfer.merge_release()
+
+
 def test_adopt_glued_cubes(transfer):
     m, groups, comm = split_of("glued")
     ref = check_merge(transfer, groups, comm)

@@ -94,6 +94,46 @@ def test_promoted_background_equals_host_upload(adja, residency):
     ref.close()
 
 
+def test_fresh_steps_beside_a_residency_build():
+    """A FRESH step's rederive (main stream) and the residency build (topo
+    stream) both match faces in the one adjacency scratch; the record builder
+    keeps them in order.  The first step's build is enqueued before its
+    rederive, the second step's rederive follows that build: both orders.
+    Background and new mesh differ in size, so records made from the other
+    mesh's adjacency cannot pass.  Residency on equals residency off, bit for
+    bit, for both steps and for a step on the background promoted from the
+    records that were built beside the rederive."""
+    m1 = M.kuhn_cube(7, seed=101)
+    sols1 = fields(m1)
+    m2, x2, t2, tets2 = new_mesh(8, 202)
+    m3, x3, t3, tets3 = new_mesh(6, 303)
+    assert m1.ne != m2.ne
+    init2 = [np.full((len(x2), s.shape[1]), -3.0) for s in sols1]
+
+    def cycle(residency):
+        tr = Transfer(0)
+        try:
+            tr.set_residency(residency)
+            tr.upload_background(m1, sols1, 0, adja=False)
+            tr.upload_points(x2, t2, tets2)
+            out = []
+            for _ in range(2):
+                tr.run(flags=N.RUN_FRESH_BACKGROUND)
+                out.append(tr.download(init=init2))
+            tr.promote_background(m2, out[-1].sols, adja=False)
+            tr.upload_points(x3, t3, tets3)
+            tr.run()
+            out.append(tr.download())
+            return out
+        finally:
+            tr.close()
+
+    on, off = cycle(True), cycle(False)
+    assert (on[0].status != 0).any() and (on[2].status != 0).any()
+    for a, b in zip(on, off):
+        compare(a, b, len(sols1))
+
+
 def test_rows_not_written_come_from_the_caller():
     """Orphan (in no valid new tet) and NUL points are not located: their rows
     of the promoted background are the caller's values."""
