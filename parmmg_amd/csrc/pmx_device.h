@@ -226,12 +226,15 @@ __device__ __forceinline__ unsigned interp_bar(const double *__restrict__ sol, c
 // LAYOUT_GEN: interp_bar<4> of pmx_device.h.
 enum { LAYOUT_GEN = 0, LAYOUT_ANI = 1, LAYOUT_ISO = 2 };
 
+// The row of a point in registers (LAYOUT_ANI: S = 6; LAYOUT_ISO), so that the
+// caller chooses how it reaches memory; false: nothing to write (a failed
+// inversion leaves the output untouched, src/interpmesh_pmmg.c:258-267).
 template <int LAYOUT, int S>
-__device__ __forceinline__ unsigned interp_layout(const double *__restrict__ sol, const SolDesc &sd,
-                                                  const int *v, const double *phi,
-                                                  double *__restrict__ out) {
+__device__ __forceinline__ bool interp_row(const double *__restrict__ sol, const int *v,
+                                           const double *phi, double r[S]) {
+  static_assert(LAYOUT == LAYOUT_ISO || (LAYOUT == LAYOUT_ANI && S == 6), "a compile-time row");
   if constexpr (LAYOUT == LAYOUT_ANI) {
-    double mint[6], r[6];
+    double mint[6];
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -243,17 +246,10 @@ __device__ __forceinline__ unsigned interp_layout(const double *__restrict__ sol
 #pragma unroll
       for (int j = 0; j < 6; j++) mint[j] = (i == 0) ? phi[i] * mi[j] : mint[j] + phi[i] * mi[j];
     }
-    // a failed inversion leaves the output untouched (src/interpmesh_pmmg.c:258-267)
-    if (!ok || !invmat(mint, r)) return 0u;
-    double2 *o = reinterpret_cast<double2 *>(out);
-    o[0] = make_double2(r[0], r[1]);
-    o[1] = make_double2(r[2], r[3]);
-    o[2] = make_double2(r[4], r[5]);
-    return 1u;
-  } else if constexpr (LAYOUT == LAYOUT_ISO) {
-    double acc[S];
+    return ok && invmat(mint, r);
+  } else {
 #pragma unroll
-    for (int j = 0; j < S; j++) acc[j] = 0.0;
+    for (int j = 0; j < S; j++) r[j] = 0.0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
       const double *row = sol + (int64_t)v[i] * S;
@@ -262,24 +258,41 @@ __device__ __forceinline__ unsigned interp_layout(const double *__restrict__ sol
 #pragma unroll
         for (int j = 0; j < S; j += 2) {
           const double2 d = *reinterpret_cast<const double2 *>(row + j);
-          acc[j] += phi[i] * d.x;
-          acc[j + 1] += phi[i] * d.y;
+          r[j] += phi[i] * d.x;
+          r[j + 1] += phi[i] * d.y;
         }
       } else {
 #pragma unroll
-        for (int j = 0; j < S; j++) acc[j] += phi[i] * row[j];
+        for (int j = 0; j < S; j++) r[j] += phi[i] * row[j];
       }
     }
-    if constexpr ((S & 1) == 0) {
+    return true;
+  }
+}
+
+// one lane's row to memory: 16-B stores where the rows are 16-B aligned
+template <int S>
+__device__ __forceinline__ void store_row(const double r[S], double *__restrict__ out) {
+  if constexpr ((S & 1) == 0) {
 #pragma unroll
-      for (int j = 0; j < S; j += 2) *reinterpret_cast<double2 *>(out + j) = make_double2(acc[j], acc[j + 1]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < S; j++) out[j] = acc[j];
-    }
-    return (1u << sd.nsol) - 1u;
+    for (int j = 0; j < S; j += 2) *reinterpret_cast<double2 *>(out + j) = make_double2(r[j], r[j + 1]);
   } else {
+#pragma unroll
+    for (int j = 0; j < S; j++) out[j] = r[j];
+  }
+}
+
+template <int LAYOUT, int S>
+__device__ __forceinline__ unsigned interp_layout(const double *__restrict__ sol, const SolDesc &sd,
+                                                  const int *v, const double *phi,
+                                                  double *__restrict__ out) {
+  if constexpr (LAYOUT == LAYOUT_GEN) {
     return interp_bar<4>(sol, sd, v, phi, out);
+  } else {
+    double r[S];
+    if (!interp_row<LAYOUT, S>(sol, v, phi, r)) return 0u;
+    store_row<S>(r, out);
+    return LAYOUT == LAYOUT_ANI ? 1u : (1u << sd.nsol) - 1u;
   }
 }
 

@@ -168,7 +168,8 @@ __device__ __forceinline__ bool face_tie(const VolArgs &A, D3 p, int &cur, TetRe
   return false;
 }
 
-// the end of a lane: interpolate, or hand the point to k_fallback
+// the end of a lane: interpolate, or hand the point to k_fallback (k_walk, and
+// k_walks for the generic layout; walk_finish_wave below for the others)
 template <int LAYOUT, int S, bool TIES>
 __device__ __forceinline__ void walk_finish(const VolArgs &A, int64_t i, D3 p, bool found, int step,
                                             int cur, TetRec &t, double lam[4], unsigned &s_cnt,
@@ -197,6 +198,85 @@ __device__ __forceinline__ void walk_finish(const VolArgs &A, int64_t i, D3 p, b
     A.bestk[slot] = 0x7fffffff;
     A.best[slot] = ~0ull;
     A.steps[i] = -step;
+  }
+}
+
+// The end of a wave of k_walks (LAYOUT_ANI / LAYOUT_ISO): walk_finish's results,
+// with the rows of a wave whose 64 points are consecutive stored as one block.
+//
+// Every lane of the wave comes here, also one past the list's end: it has
+// walked no step (every listed point counts one step or more).
+// A lane has a row when its point is found, stays out of the tie and stuck
+// lists and its interpolation wrote something.  A lane's own stores scatter
+// 8-16-B pieces at a stride of 8 S bytes: three instructions over the 40
+// 64-B segments of a wave's rows at S = 5.  When every lane has a row and
+// lane l holds point i0 + l (the classification's compaction keeps the input
+// order, so that is the normal case), the rows are 64 S consecutive doubles:
+// they pass through the wave's own LDS slice and leave as S stores of 512
+// consecutive bytes, 8-9 segments each.  Any other wave (a hole in its list
+// window, a tie or stuck lane, a failed inversion, the tail) stores per lane,
+// as walk_finish does.  The same doubles reach the same addresses either way.
+// A located lane loads its solution rows before it stores anything: loads and
+// stores share one in-order counter, so a store issued first would make the
+// first use of a row wait for its acknowledgement as well.
+template <int LAYOUT, int S, bool TIES>
+__device__ __forceinline__ void walk_finish_wave(const VolArgs &A, int64_t i, D3 p, bool found,
+                                                 int step, int cur, TetRec &t, double lam[4],
+                                                 unsigned &s_cnt, unsigned &s_sum, unsigned &s_max,
+                                                 unsigned &s_min) {
+  __shared__ double rows[4][64 * S];               // a slice per wave of the 256-thread block
+  bool located = false;
+  if (step != 0) {
+    if (found) {
+      double lmn = fmin(fmin(lam[0], lam[1]), fmin(lam[2], lam[3]));
+      if (lmn < TIE_NEAR && (!TIES || face_tie(A, p, cur, t, lam))) {
+        // within the tolerance of several tets: canonical tet by the BFS
+        unsigned slot = atomicAdd(A.tie_count, 1u);
+        A.tie_list[slot] = make_int2((int)i, cur);
+        A.steps[i] = step;
+      } else {
+        located = true;
+      }
+    } else {
+      unsigned slot = atomicAdd(A.stuck_count, 1u);
+      A.stuck_list[slot] = (int)i;
+      A.found[slot] = 0x7fffffff;
+      A.bestk[slot] = 0x7fffffff;
+      A.best[slot] = ~0ull;
+      A.steps[i] = -step;
+    }
+  }
+  double r[S];
+  bool row = false;
+  if (located) {
+    const int v[4] = {t.v[0], t.v[1], t.v[2], t.v[3]};
+    row = interp_row<LAYOUT, S>(A.sol, v, lam, r);
+  }
+  const int lane = threadIdx.x & 63;
+  const int i0 = __builtin_amdgcn_readfirstlane((int)i);
+  if (__all(row && (int)i == i0 + lane)) {
+    double *w = rows[threadIdx.x >> 6];
+#pragma unroll
+    for (int k = 0; k < S; k++) w[lane * S + k] = r[k];
+    // the wave reads what its other lanes wrote: LDS serves a wave's accesses
+    // in order; the fences and the barrier keep the compiler to that order
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    double *o = A.out + (int64_t)i0 * S;
+#pragma unroll
+    for (int k = 0; k < S; k++) o[64 * k + lane] = w[64 * k + lane];
+  } else if (row) {
+    store_row<S>(r, A.out + i * S);
+  }
+  if (located) {
+    A.elem[i] = cur;
+    A.status[i] = 1;
+    A.steps[i] = step;
+    const unsigned wm = !row ? 0u : LAYOUT == LAYOUT_ANI ? 1u : (1u << A.sd.nsol) - 1u;
+    A.wmask[i] = (uint8_t)(wm | A.const_bit);
+    s_cnt += 1; s_sum += step;
+    s_max = max(s_max, (unsigned)step); s_min = min(s_min, (unsigned)step);
   }
 }
 
@@ -369,16 +449,22 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
   const int64_t b = walk_xcd_remap(blockIdx.x, gridDim.x);
   const int64_t j = b * blockDim.x + threadIdx.x;
   unsigned s_cnt = 0, s_sum = 0, s_max = 0, s_min = 0xffffffffu;
+  // a lane's state at the end of its walk, for the wave's common epilogue
+  // (step stays 0 in a lane past the list's end, and only there)
+  int64_t i = 0;
+  D3 p{0.0, 0.0, 0.0};
+  TetRec t;
+  int cur = 0, step = 0;
+  bool found = false;
+  double lam[4];
 
   if (j < *A.nlist_dev) {     // the step's count (the grid is sized by an upper bound)
     // the list keeps the input order (order-preserving compaction): the
     // point reads through it are as coalesced as the list itself (r03: a
     // list-ordered copy of the coordinates saved the walk 1 % and cost the
     // classification 0.15 ms of copying)
-    const int64_t i = A.list[j];
-    const D3 p{A.q[3 * i], A.q[3 * i + 1], A.q[3 * i + 2]};
-    TetRec t;
-    int cur;
+    i = A.list[j];
+    p = D3{A.q[3 * i], A.q[3 * i + 1], A.q[3 * i + 2]};
     if constexpr (PM) {
       cur = A.grid[j];
       t = walk_rec<CW>(A, cur, FAR && A.exp == 17);
@@ -390,9 +476,6 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
     int ring[WALK_RING];
 #pragma unroll
     for (int r = 0; r < WALK_RING; r++) ring[r] = 0;
-    int step = 0;
-    bool found = false;
-    double lam[4];
     if (t.v[0] <= 0) step = 1;                  // !MG_EOK start: let the scan decide
     else {
       D3 C[4] = {ld3(A.xyz, t.v[0]), ld3(A.xyz, t.v[1]), ld3(A.xyz, t.v[2]), ld3(A.xyz, t.v[3])};
@@ -512,7 +595,11 @@ __global__ __launch_bounds__(256) void k_walks(VolArgs A) {
         }
       }
     }
-    walk_finish<LAYOUT, S, TIES>(A, i, p, found, step, cur, t, lam, s_cnt, s_sum, s_max, s_min);
+  }
+  if constexpr (LAYOUT == LAYOUT_GEN) {       // S known at run time only: per-lane stores
+    if (step != 0) walk_finish<LAYOUT, S, TIES>(A, i, p, found, step, cur, t, lam, s_cnt, s_sum, s_max, s_min);
+  } else {
+    walk_finish_wave<LAYOUT, S, TIES>(A, i, p, found, step, cur, t, lam, s_cnt, s_sum, s_max, s_min);
   }
   wave_stats_w(A.wstats + (b * blockDim.x + threadIdx.x) / 64, s_cnt, s_sum, s_max, s_min);
 }
