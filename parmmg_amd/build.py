@@ -26,8 +26,8 @@ MESHGEN_SO = os.path.join(PKG, "libpmx_meshgen.so")
 ORACLE_SO = os.path.join(ORACLE, "liboracle.so")
 
 HIP_SOURCES = ["pmx_capi.hip", "pmx_background.hip", "pmx_kernels.hip", "pmx_walk.hip", "pmx_bdy.hip",
-               "pmx_stats.hip", "pmx_groups.hip", "pmx_topo.hip", "pmx_medit.hip", "pmx_more.hip",
-               "pmx_contig.hip", "pmx_split.hip", "pmx_merge.hip"]
+               "pmx_quality.hip", "pmx_lengths.hip", "pmx_graph.hip", "pmx_reduce.hip", "pmx_groups.hip",
+               "pmx_topo.hip", "pmx_medit.hip", "pmx_more.hip", "pmx_contig.hip", "pmx_split.hip", "pmx_merge.hip"]
 HIPCC_FLAGS = [
     "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",
     "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function",

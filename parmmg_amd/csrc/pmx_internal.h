@@ -427,8 +427,34 @@ extern "C" int pmx_timing_reset(pmx_ctx *ctx);
 // pmx_kernel_ms(ctx, 7): the batch kernels of the last pmx_interp_more (pmx_more.hip)
 double pmx_more_kernel_ms(pmx_ctx *ctx);
 // pmx_kernel_ms(ctx, 8..11): the last pmx_metis_graph -- its kernels summed,
-// the count, the scan, the fill (pmx_stats.hip)
+// the count, the scan, the fill (pmx_graph.hip)
 double pmx_graph_kernel_ms(pmx_ctx *ctx, int which);
+// Partial records per statistics pass, a function of ne only, and the width of
+// the fixed-order final reduction's first level (pmx_quality.hip)
+#define FINAL_GRID 64
+int stat_blocks(int64_t ne);
+// d_tetv, the quality pass's 16-B connectivity stream, derived from the tet
+// records on first use after an upload (pmx_quality.hip)
+bool ensure_tetv(pmx_ctx *ctx);
+// the statistics' view of the uploaded group; tetv false: without d_tetv
+// (pmx_quality.hip)
+bool stat_args(const pmx_call &C, StatArgs &A, bool tetv = true);
+// d_red, the passes' partial records, at least `bytes` (pmx_quality.hip)
+bool ensure_red(pmx_ctx *ctx, size_t bytes);
+// metRidTyp is 0 or 1 (pmx_quality.hip)
+bool check_met_rid_typ(const pmx_call &C, int metRidTyp);
+// The lengths' view of the group on A, after stat_args: ridge storage from
+// metRidTyp and the metric size -- refused without the point tags --, the
+// surface arrays when they are uploaded (pmx_lengths.hip)
+bool length_view(const pmx_call &C, int metRidTyp, StatArgs &A);
+// a public partial record as the statistics the host wrappers return (pmx_reduce.hip)
+void qual_to_stats(const pmx_qual_part &r, pmx_qual_stats *st);
+void len_to_stats(const pmx_len_part &r, pmx_len_stats *st);
+// the public record (pmx_qual_part / pmx_len_part) that a host wrapper's
+// device call left in d_pub, on the host
+template <class R> inline bool read_pub(const pmx_call &C, R &r) {
+  return C.read_words(&r, (const R *)C.ctx->d_pub.p, 1, "download");
+}
 // pmx_kernel_ms(ctx, 12 / 13): the labelling / the replay and recolour kernels
 // of the last pmx_contiguity or pmx_fix_contiguity, summed (pmx_contig.hip)
 double pmx_contig_kernel_ms(pmx_ctx *ctx, int which);

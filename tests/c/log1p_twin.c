@@ -1,4 +1,4 @@
-/* The device's pmx_log1p (parmmg_amd/csrc/pmx_stats.hip) in plain C: glibc's
+/* The device's pmx_log1p (parmmg_amd/csrc/pmx_metric.h) in plain C: glibc's
  * log1p algorithm (sysdeps/ieee754/dbl-64/s_log1p.c, Sun's fdlibm with the
  * pairwise polynomial) -- compared bit for bit with the host's log1p by
  * tests/test_oracle.py (test infrastructure).  Build: -O2 -ffp-contract=off. */

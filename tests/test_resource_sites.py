@@ -14,6 +14,9 @@ RAW_CALLS = ["hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEve
 ALLOWED = {"pmx_capi.hip": {"pmx_device_alloc": {"hipMalloc(": 1, "hipFree(": 1},   # the free: its memset failed
                             "pmx_device_free": {"hipFree(": 1}}}
 GONE = ["free_all", "sp_free", "dfree(", "MCK(", "struct Scratch"]
+# files whose host code checks every HIP call through the call helper
+# (pmx_host.h: pmx_call, PMX_CK): no comparison with hipSuccess by hand
+ON_CALL_HELPER = ["pmx_quality.hip", "pmx_lengths.hip", "pmx_graph.hip", "pmx_reduce.hip"]
 
 
 def _sources():
@@ -62,3 +65,10 @@ def test_hand_kept_lists_are_gone():
     for f, text in _sources():
         for word in GONE:
             assert word not in text, f"{f}: {word}"
+
+
+def test_converted_files_hold_no_hand_checks():
+    texts = dict(_sources())
+    for f in ON_CALL_HELPER:
+        assert f in texts, f"{f}: no such file (renamed? keep the list in step)"
+        assert "hipSuccess" not in texts[f], f"{f}: a hand-written hipSuccess check"
