@@ -10,9 +10,12 @@
 // flags in the state PMMG_precompute_nodeTrias leaves them (number of incident
 // trias), with mesh->base = query ordinal + 1.  The flags a query writes
 // (visited trias, wedge/cone marks) are kept in thread-private lists.
+//
+// Every kernel that walks the surface lives here, the sequential mode's
+// replay (k_seq_resolve) included; the fans the walks read are built in
+// pmx_fans.hip, the sequential modes are driven from pmx_seq.hip.
 #include "pmx_device.h"
 #include "pmx_kernels.h"
-#include <hipcub/hipcub.hpp>
 #include "pmx_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -20,41 +23,6 @@
 #define UNSET (-1)
 
 __device__ __constant__ int NXT2d[6] = {1, 2, 0, 1, 2, 0};
-
-struct BdyArgs {
-  const double *xyz;        // old vertices, 24 B
-  const TriRec *tris;
-  const Pt4 *trn;
-  const int2 *ntrange;      // fan [lo, hi) in ntlist of vertex l of tria k, at 3 k + l
-  const int *ntlist;
-  const double *sol;
-  SolDesc sd;
-  const double *q;          // new points, dense x y z (0-based)
-  const int8_t *kind;
-  int64_t nq, nt;
-  double hausd;
-  const int *grid;     // tria hint grid (shares GridDesc with the tet grid); a
-                       // PMX_RUN_POINTMAP step: the start tria of every list entry
-  GridDesc g;
-  double *out;
-  uint8_t *wmask;
-  int *elem, *status, *steps, *start, *edge, *vertex;
-  Pt4 *bphi;           // (non-null, nlist entries) per entry of `list`: the 3 barycentrics the point's fields were
-                       // interpolated with, in the tria's vertex order (pmx_interp_more)
-  int *stuck_list;     // bdy exhaustive list
-  unsigned *stuck_count;
-  int *ovf_list;       // private-list overflow
-  unsigned *ovf_count;
-  const int *list;       // indices of the boundary points
-  int64_t nlist;         // upper bound (launch size); the step's count is *nlist_dev
-  const int *nlist_dev;
-  uint4 *wstats;         // per-wave walk statistics
-  // PMX_RUN_SEQUENTIAL_SURFACE's speculative pass: per point its start tria
-  // and mesh->base (null: the hint tria, ordinal + 1), and whether the walk
-  // ran a shadow-wedge test (the only path to the point flags)
-  const int *seq_start, *seq_base;
-  uint8_t *seq_w;
-};
 
 // thread-private query state: visited trias + point-flag overrides
 template <int CAP> struct RegState {
@@ -91,7 +59,6 @@ struct GlobHashState {
   int mask = 0, gen = 0, nv = 0, no = 0, capv = 0;
   bool over = false;
 };
-#define GHS_SLOTS 4096           // per table and thread; at most half of them used
 __device__ __forceinline__ unsigned ghs_hash(int x) { return (unsigned)x * 2654435761u; }
 __device__ bool visited(GlobHashState &s, int t) {
   for (unsigned h = ghs_hash(t) & s.mask;; h = (h + 1) & s.mask) {
@@ -132,8 +99,8 @@ __device__ void set_flag(GlobHashState &s, int p, int f) {
 
 // the reference's own state, for the sequential replay (one lane): tria
 // flags tf[] compared with mesh->base, point flags pf[] kept across queries
-// (PF_INIT: still the incident-tria count PMMG_precompute_nodeTrias left)
-#define PF_INIT ((int)0x80808080)
+// (PF_INIT, pmx_kernels.h: still the incident-tria count
+// PMMG_precompute_nodeTrias left)
 struct SeqState {
   int *tf, *pf;
   int base;
@@ -604,12 +571,12 @@ __global__ __launch_bounds__(64) void k_locate_bdy_ovf(BdyArgs A, int *ws, int c
 }
 
 // the sequential mode's overflow pass, on hashed lists (workspace:
-// ghs_ws_ints() ints per thread, zeroed by the caller)
+// GHS_WS_INTS ints per thread, zeroed by the caller)
 __global__ __launch_bounds__(64) void k_locate_bdy_ovf_hash(BdyArgs A, int *ws) {
   const unsigned n = *A.ovf_count;
   const unsigned nthr = gridDim.x * blockDim.x;
   const unsigned tid = blockIdx.x * blockDim.x + threadIdx.x;
-  int *w = ws + (size_t)tid * (GHS_SLOTS * 6);
+  int *w = ws + (size_t)tid * GHS_WS_INTS;
   for (unsigned j = tid; j < n; j += nthr) {
     int64_t i = A.ovf_list[j];
     const D3 p = ld3(A.q, (int)i);
@@ -730,9 +697,6 @@ __device__ __forceinline__ void tria_hint_one(const TriRec *tris, const double *
   int cz = (int)fmin(fmax((m.z - g.lo[2]) * g.inv[2], 0.0), (double)(g.dim[2] - 1));
   atomicMax(&grid[(int64_t)cx + (int64_t)g.dim[0] * ((int64_t)cy + (int64_t)g.dim[1] * cz)], (int)k);
 }
-
-// tria hint grid: cell -> largest tria index whose centroid falls in it
-// (deterministic: the surface semantics depend on the start triangle)
 __global__ __launch_bounds__(256) void k_tria_hint_build(const TriRec *tris, const double *xyz,
                                                          int64_t nt, int *grid, GridDesc g) {
   for (int64_t k = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt;
@@ -768,307 +732,6 @@ __device__ int tria_hint(const BdyArgs &A, D3 p) {
 // C3 within 0.1 %; profiles/r03_c{2,3}_sweep_bdy_cap.log)
 #define BDY_CAP 16
 #define OVF_CAP 2048
-#define OVF_THREADS (64 * 64)
-
-// node -> trias graph (the content of PMMG_precompute_nodeTrias,
-// src/locate_pmmg.c:134-195: each boundary vertex's fan of trias in increasing
-// tria index, and the fan sizes the point flags start from), rebuilt by every
-// step that rebuilds the background's derived data -- the reference builds it
-// inside PMMG_interpMetricsAndFields (src/interpmesh_pmmg.c:707).  Sized by
-// the surface, not the volume: the 3 nt (vertex, 3 k + l) pairs are radix
-// sorted by vertex (stable: fans in tria order), and every pair's slot 3 k + l
-// records its vertex's run [lo, hi) -- the surface kernels always reach a
-// vertex through a tria that holds it, so no per-vertex offsets over np.
-// PMMG_precompute_nodeTrias (src/locate_pmmg.c:134-195): per boundary
-// vertex, its incident boundary trias in ascending tria order, i.e. what a
-// stable sort of the (vertex, 3 k + l) pairs gives.  Two builds with the same
-// output, chosen by size (r03, C2 / C3 steps):
-//  * a counting sort over the vertex ids -- count -> exclusive scan over np ->
-//    fill at the vertex's offset (slot by atomic, order arbitrary) -> the
-//    slot-0 writer sorts its fan (a few entries): its arrays are np-sized;
-//  * a 25-bit radix sort of the 3 nt pairs (hipCUB): latency-bound passes
-//    whose cost does not grow with np.
-// With np > 5 * 3 nt (C3: 16.8 M vertices, 2.3 M pairs) the counting sort's
-// memset and scan over np competed with the main stream's derived-data pass
-// (step 2.11 -> 2.20 ms); at C2 (1.7 M vertices, 0.5 M pairs) the radix
-// sort's passes were the surface stream's critical path (step 0.44 -> 0.36
-// ms with the counting sort).  A compacted-id counting sort (bitmap of the
-// boundary vertices) lost both: 2.3 M atomicOr on 525 K words serialise.
-__global__ __launch_bounds__(256) void k_nt_count(const TriRec *__restrict__ tris, int64_t nt,
-                                                  unsigned *__restrict__ cnt) {
-  for (int64_t k = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt;
-       k += (int64_t)gridDim.x * blockDim.x) {
-    const TriRec t = tris[k];
-    if (t.v[0] <= 0) continue;
-    for (int l = 0; l < 3; l++) atomicAdd(&cnt[t.v[l]], 1u);
-  }
-}
-__global__ __launch_bounds__(256) void k_nt_fill(const TriRec *__restrict__ tris, int64_t nt,
-                                                 const unsigned *__restrict__ off, unsigned *__restrict__ cnt,
-                                                 int *__restrict__ list, int2 *__restrict__ range,
-                                                 uint8_t *__restrict__ own) {
-  for (int64_t k = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt;
-       k += (int64_t)gridDim.x * blockDim.x) {
-    const TriRec t = tris[k];
-    for (int l = 0; l < 3; l++) {
-      if (t.v[0] <= 0) { range[3 * k + l] = make_int2(0, 0); own[3 * k + l] = 0; continue; }
-      const int v = t.v[l];
-      const unsigned lo = off[v], hi = off[v + 1];
-      const unsigned left = atomicSub(&cnt[v], 1u);          // hi - lo, ..., 1
-      list[lo + left - 1] = (int)k;
-      range[3 * k + l] = make_int2((int)lo, (int)hi);
-      own[3 * k + l] = left == 1u ? 1 : 0;                   // exactly one writer per fan
-    }
-  }
-}
-__global__ __launch_bounds__(256) void k_nt_sort(int64_t nt, const int2 *__restrict__ range,
-                                                 const uint8_t *__restrict__ own, int *__restrict__ list) {
-  for (int64_t i = 3 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * (nt + 1);
-       i += (int64_t)gridDim.x * blockDim.x) {
-    if (!own[i]) continue;
-    const int2 r = range[i];
-    for (int a = r.x + 1; a < r.y; a++) {                 // insertion sort of the fan
-      const int x = list[a];
-      int b = a - 1;
-      while (b >= r.x && list[b] > x) { list[b + 1] = list[b]; b--; }
-      list[b + 1] = x;
-    }
-  }
-}
-__global__ __launch_bounds__(256) void k_nt_pairs(const TriRec *__restrict__ tris, int64_t nt,
-                                                  unsigned *__restrict__ key, int *__restrict__ val) {
-  for (int64_t k = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt;
-       k += (int64_t)gridDim.x * blockDim.x) {
-    const TriRec t = tris[k];
-    for (int l = 0; l < 3; l++) {
-      key[3 * (k - 1) + l] = (unsigned)t.v[l];
-      val[3 * (k - 1) + l] = (int)(3 * k + l);
-    }
-  }
-}
-__global__ __launch_bounds__(256) void k_nt_runs(const unsigned *__restrict__ key, const int *__restrict__ val,
-                                                 int64_t m, int2 *__restrict__ range, int *__restrict__ list) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-    list[i] = val[i] / 3;
-    if (i > 0 && key[i - 1] == key[i]) continue;           // not the start of a run
-    int64_t j = i + 1;
-    while (j < m && key[j] == key[i]) j++;
-    for (int64_t q = i; q < j; q++) range[val[q]] = make_int2((int)i, (int)j);
-  }
-}
-
-
-// The fans by rotation (r05), for a closed manifold surface -- every
-// boundary of a ParMmg group's volume mesh, interfaces included: each
-// (tria, corner) slot walks its vertex's fan through the tria adjacency
-// (Mmg's adjt: edge i opposite vertex i) and writes its tria into the window
-// of the fan's owner (its smallest tria) at its rank: the fan's increasing
-// tria order of PMMG_precompute_nodeTrias.  One kernel, no atomics, no
-// np-sized arrays (the radix sort of C3's 2.3 M (vertex, tria) pairs took
-// ~0.26 ms alone on the GPU).  A fan that meets an
-// edge without a neighbour (open or non-manifold surface), a neighbour
-// without the vertex, or more than FAN_CAP trias counts in *bad: the upload
-// runs it once as a check, and a background with any such fan keeps the sort.
-#define FAN_CAP 32
-// one turn around v from tria k (corner l), the record of each tria in a
-// register (one dependent load per step); f(tria, corner of v) per tria, k
-// first; false if the fan does not close within FAN_CAP trias
-__device__ __forceinline__ int sel3(const int a[3], int i) { return i == 0 ? a[0] : i == 1 ? a[1] : a[2]; }
-template <class F>
-__device__ __forceinline__ bool fan_turn(const TriRec *__restrict__ tris, int k, int l, const TriRec &t0, F f) {
-  const int v = sel3(t0.v, l);
-  TriRec tc = t0;
-  int cx = (l + 1) % 3, w = sel3(t0.v, (l + 2) % 3);
-  f(k, l);
-  for (int n = 1;; n++) {
-    const int nxt = sel3(tc.nb, cx);               // across the edge {v, w}
-    if (nxt == k) return true;                     // closed
-    if (nxt <= 0 || n == FAN_CAP) return false;
-    tc = tris[nxt];
-    const int cv = tc.v[0] == v ? 0 : tc.v[1] == v ? 1 : tc.v[2] == v ? 2 : -1;
-    const int cw = tc.v[0] == w ? 0 : tc.v[1] == w ? 1 : tc.v[2] == w ? 2 : -1;
-    if (cv < 0 || cw < 0 || cv == cw || tc.v[0] <= 0) return false;
-    f(nxt, cv);
-    w = sel3(tc.v, 3 - cv - cw);                   // the other edge at v: {v, w'}
-    cx = cw;
-  }
-}
-// Every slot walks its fan once: the fan's window is its owner's (the
-// smallest tria), and the slot's tria goes to the window at its rank in the
-// fan (the number of smaller members) -- the sorted fan without a sort and no
-// dependent chain beyond the walk itself.  r05 A/Bs at C3 (rocprof, beside
-// the main stream): this 0.12 ms; an owner sorting its fan in global memory
-// (a ~35-deep dependent chain) 0.19 ms; only the local minima walking and the
-// owner sorting in LDS (2.3 M walks -> 0.8 M, but serial chains in few
-// threads) 0.23 ms, step 2.061 vs 2.042 ms (profiles/r05_c3_sweep_fans_owner_lds.log).
-// vown (the check only): each fan's owner slot writes its window base at
-// its vertex; k_fan_check then finds the vertices whose slots belong to more
-// than one fan (two surface sheets touching at a vertex: a group pinched
-// there), which the rotation alone cannot see.  No per-vertex counts, no
-// np-sized memset: every surface vertex has at least one fan owner, and no
-// other vertex is read.  (r06 first version: a per-vertex tria count by
-// atomics after an np-sized memset, 0.24 ms at C3 beside the step's prefix.)
-__global__ __launch_bounds__(256) void k_fan_rotate(const TriRec *__restrict__ tris, int64_t nt,
-                                                    int2 *__restrict__ range, int *__restrict__ list,
-                                                    unsigned *__restrict__ bad, int *__restrict__ vown) {
-  unsigned nbad = 0;
-  for (int64_t i = 3 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * (nt + 1);
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int k = (int)(i / 3), l = (int)(i - 3 * (int64_t)k);
-    const TriRec t0 = tris[k];
-    if (t0.v[0] <= 0) { range[i] = make_int2(0, 0); continue; }
-    int n = 0, rank = 0, own = k, lown = l;
-    const bool ok = fan_turn(tris, k, l, t0, [&](int g, int c) {
-      n++;
-      rank += g < k ? 1 : 0;
-      if (g < own) { own = g; lown = c; }
-    });
-    if (!ok) { nbad++; range[i] = make_int2(0, 0); continue; }
-    const int base = (int)((3 * (int64_t)own + lown - 3) * FAN_CAP);
-    range[i] = make_int2(base, base + n);
-    list[base + rank] = k;
-    if (vown && own == k && lown == l) vown[sel3(t0.v, l)] = base;
-  }
-  for (int o = 32; o > 0; o >>= 1) nbad += __shfl_xor(nbad, o);
-  if ((threadIdx.x & 63) == 0 && nbad) atomicAdd(bad, nbad);
-}
-__global__ __launch_bounds__(256) void k_fan_check(const TriRec *__restrict__ tris, int64_t nt,
-                                                   const int2 *__restrict__ range, const int *__restrict__ vown,
-                                                   unsigned *__restrict__ bad) {
-  unsigned nbad = 0;
-  for (int64_t i = 3 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * (nt + 1);
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int2 r = range[i];
-    if (r.y <= r.x) continue;                      // deleted tria (a failed fan is counted already)
-    const int k = (int)(i / 3), l = (int)(i - 3 * (int64_t)k);
-    const int v = tris[k].v[l];
-    if (vown[v] != r.x) nbad++;
-  }
-  for (int o = 32; o > 0; o >>= 1) nbad += __shfl_xor(nbad, o);
-  if ((threadIdx.x & 63) == 0 && nbad) atomicAdd(bad, nbad);
-}
-
-bool pmx_ctx::fan_rotation(hipStream_t s, unsigned *d_bad, bool check) {
-  const int64_t m = 3 * nt;
-  if (!pmx_dgrow(this, d_ntrange, (size_t)(3 * (nt + 1))) || !pmx_dgrow(this, d_ntlist, (size_t)(m * FAN_CAP)))
-    return false;
-  if (check && !pmx_dgrow(this, d_ntkey, (size_t)(np + 2))) return false;
-  int *vown = check ? reinterpret_cast<int *>(d_ntkey.p) : nullptr;
-  const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, 16384));
-  hipLaunchKernelGGL(k_fan_rotate, dim3(nb), dim3(256), 0, s, d_tris.p, nt, d_ntrange.p, d_ntlist.p, d_bad,
-                     vown);
-  if (check)
-    hipLaunchKernelGGL(k_fan_check, dim3(nb), dim3(256), 0, s, d_tris.p, nt, (const int2 *)d_ntrange.p,
-                       (const int *)vown, d_bad);
-  if (hipGetLastError() != hipSuccess) {
-    err = "node trias: launch";
-    return false;
-  }
-  return true;
-}
-
-// the upload's check: the fans of this background by rotation, their
-// failures (open, non-manifold, pinched, over FAN_CAP) into h_nbad[4] (read
-// after the upload's final sync).
-// PMX_FAN_ROTATION=0 keeps the sort (A/B, tests).
-bool pmx_ctx::check_fans(hipStream_t s) {
-  fan_rot = false;
-  h_nbad.p[4] = 1u;
-  if (nt < 1 || 3 * (nt + 1) * (int64_t)FAN_CAP > (int64_t)INT32_MAX) return true;   // int windows
-  const char *e = getenv("PMX_FAN_ROTATION");
-  if (e && e[0] == '0') return true;
-  // the vertices' fan owners (np-sized, no memset): a vertex where several
-  // surface sheets touch has more than one fan
-  if (!pmx_dgrow(this, d_wfar, 8)) return false;
-  if (!pmx_dgrow(this, d_ntkey, (size_t)(np + 2)) ||
-      !pmx_dgrow(this, d_ntrange, (size_t)(3 * (nt + 1))) || !pmx_dgrow(this, d_ntlist, (size_t)(3 * nt * FAN_CAP))) {
-    // no room for the check or the fan windows (32 per tria corner): the
-    // surface keeps the sort-built fans, the upload goes on
-    (void)hipGetLastError();
-    err.clear();
-    return true;
-  }
-  if (hipMemsetAsync(d_wfar.p + 3, 0, sizeof(unsigned), s) != hipSuccess) {
-    err = "node trias: memset";
-    return false;
-  }
-  if (!fan_rotation(s, d_wfar.p + 3, true)) return false;
-  if (hipMemcpyAsync(h_nbad.p + 4, d_wfar.p + 3, sizeof(unsigned), hipMemcpyDeviceToHost, s) != hipSuccess) {
-    err = "node trias: check";
-    return false;
-  }
-  return true;
-}
-
-// the counting sort over the vertex ids
-static bool node_trias_counting(pmx_ctx *c, hipStream_t s) {
-  const int64_t m = 3 * c->nt, np = c->np, nt = c->nt;
-  if (!pmx_dgrow(c, c->d_ntkey, (size_t)(2 * (np + 2))) || !pmx_dgrow(c, c->d_ntval, (size_t)(3 * (nt + 1))) ||
-      !pmx_dgrow(c, c->d_ntrange, (size_t)(3 * (nt + 1))) || !pmx_dgrow(c, c->d_ntlist, (size_t)m))
-    return false;
-  unsigned *cnt = c->d_ntkey.p, *off = c->d_ntkey.p + (np + 2);
-  uint8_t *own = reinterpret_cast<uint8_t *>(c->d_ntval.p);
-  size_t bytes = 0;
-  hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, off, (int)(np + 2), s);
-  if (!pmx_dgrow(c, c->d_nttmp, bytes)) return false;
-  if (hipMemsetAsync(cnt, 0, (size_t)(np + 2) * sizeof(unsigned), s) != hipSuccess) {
-    c->err = "node trias: memset";
-    return false;
-  }
-  const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nt + 255) / 256, 4096));
-  hipLaunchKernelGGL(k_nt_count, dim3(nb), dim3(256), 0, s, c->d_tris.p, nt, cnt);
-  if (hipcub::DeviceScan::ExclusiveSum(c->d_nttmp.p, bytes, cnt, off, (int)(np + 2), s) != hipSuccess) {
-    c->err = "node trias: scan";
-    return false;
-  }
-  hipLaunchKernelGGL(k_nt_fill, dim3(nb), dim3(256), 0, s, c->d_tris.p, nt, (const unsigned *)off, cnt,
-                     c->d_ntlist.p, c->d_ntrange.p, own);
-  const unsigned ns = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, 4096));
-  hipLaunchKernelGGL(k_nt_sort, dim3(ns), dim3(256), 0, s, nt, (const int2 *)c->d_ntrange.p,
-                     (const uint8_t *)own, c->d_ntlist.p);
-  return true;
-}
-
-bool pmx_ctx::build_node_trias(hipStream_t s, bool check) {
-  const int64_t m = 3 * nt;
-  if (m < 1) return true;
-  // check: the upload's check again (a FRESH step: what a new background
-  // costs), the vertices' fan owners beside the rotation
-  if (fan_rot) return fan_rotation(s, d_wfar.p + 2, check);
-  if (np <= 5 * m) {
-    if (!node_trias_counting(this, s)) return false;
-    if (hipGetLastError() != hipSuccess) {
-      err = "node trias: launch";
-      return false;
-    }
-    return true;
-  }
-  int bits = 1;
-  while (bits < 32 && ((int64_t)1 << bits) <= np) bits++;
-  if (!pmx_dgrow(this, d_ntkey, (size_t)(2 * m)) || !pmx_dgrow(this, d_ntval, (size_t)(2 * m)) ||
-      !pmx_dgrow(this, d_ntrange, (size_t)(3 * (nt + 1))) || !pmx_dgrow(this, d_ntlist, (size_t)m))
-    return false;
-  size_t bytes = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const unsigned *)nullptr, (unsigned *)nullptr,
-                                     (const int *)nullptr, (int *)nullptr, (int)m, 0, bits, s);
-  if (!pmx_dgrow(this, d_nttmp, bytes)) return false;
-  const unsigned nb = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nt + 255) / 256, 4096));
-  hipLaunchKernelGGL(k_nt_pairs, dim3(nb), dim3(256), 0, s, d_tris.p, nt, d_ntkey.p, d_ntval.p);
-  if (hipcub::DeviceRadixSort::SortPairs(d_nttmp.p, bytes, (const unsigned *)d_ntkey.p, d_ntkey.p + m,
-                                         (const int *)d_ntval.p, d_ntval.p + m, (int)m, 0, bits, s) !=
-      hipSuccess) {
-    err = "node trias: sort";
-    return false;
-  }
-  const unsigned nr = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 255) / 256, 8192));
-  hipLaunchKernelGGL(k_nt_runs, dim3(nr), dim3(256), 0, s, (const unsigned *)d_ntkey.p + m,
-                     (const int *)d_ntval.p + m, m, d_ntrange.p, d_ntlist.p);
-  if (hipGetLastError() != hipSuccess) {
-    err = "node trias: launch";
-    return false;
-  }
-  return true;
-}
 
 // the coarser tria hint grid over the background bbox: cells of about 8
 // boundary trias.  The grid is 3-D but only its surface cells are used, so it
@@ -1092,12 +755,11 @@ bool pmx_ctx::size_tria_grid() {
     cells *= d;
   }
   tcells = nt > 0 ? cells : 0;
-  if (tcells && !pmx_dgrow(this, d_tgrid, (size_t)cells)) { err = "hipMalloc tgrid"; return false; }
-  return true;
+  return !tcells || pmx_call{this, "tria hint grid"}.grow(d_tgrid, (size_t)cells);
 }
 
 // the surface kernels' arguments for the step's points (tria hint grid tgd)
-static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap = false) {
+BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap) {
   BdyArgs B{};
   B.xyz = c->d_xyz.p; B.tris = c->d_tris.p; B.trn = c->d_trn.p; B.ntrange = c->d_ntrange.p; B.ntlist = c->d_ntlist.p;
   B.sol = c->d_sol.p; B.sd = a.sd; B.q = c->d_qxyz.p; B.kind = c->d_kind.p; B.nq = c->nq; B.nt = c->nt;
@@ -1112,12 +774,8 @@ static BdyArgs bdy_args(pmx_ctx *c, const VolArgs &a, bool pointmap = false) {
   return B;
 }
 
-// the walks, their private-list overflow pass and the exhaustive scan
-// ovf_threads: the overflow pass's threads, OVF_THREADS unless the caller
-// sized the workspace for more (the sequential mode's speculative pass, whose
-// walks from the predecessors' trias overflow by the thousand)
-static void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_threads = OVF_THREADS,
-                             bool hashed = false, bool pointmap = false) {
+// the walks, their private-list overflow pass and the exhaustive scan (pmx_kernels.h)
+void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_threads, bool hashed, bool pointmap) {
   const int64_t nb = (B.nlist + 255) / 256;
   if (pointmap)
     hipLaunchKernelGGL((k_locate_bdy<BDY_CAP, true>), dim3((unsigned)nb), dim3(256), 0, s, B);
@@ -1127,161 +785,29 @@ static void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_
     hipLaunchKernelGGL(k_locate_bdy_ovf_hash, dim3(ovf_threads / 64), dim3(64), 0, s, B, ows);
   else
     hipLaunchKernelGGL(k_locate_bdy_ovf, dim3(ovf_threads / 64), dim3(64), 0, s, B, ows, OVF_CAP);
-  hipLaunchKernelGGL(k_exh_bdy, dim3(256), dim3(256), 0, s, B);
+  launch_exh_bdy(B, 256, s);
 }
 
 bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
-  if (nt < 1) { err = "surface points present but the background has no boundary trias"; return false; }
-  if (!pmx_dgrow(this, d_blist, (size_t)nq)) { err = "hipMalloc blist"; return false; }
-  if (!pmx_dgrow(this, d_olist, (size_t)nq)) { err = "hipMalloc olist"; return false; }
-  if (!pmx_dgrow(this, d_bphi, (size_t)std::max<int64_t>(nq_bdy_ub, 1))) return false;
-  // allocated once (the sequential mode grows it for its own pass)
-  if (!d_ows.p && !pmx_dgrow(this, d_ows, (size_t)OVF_THREADS * 3 * OVF_CAP)) { err = "hipMalloc ows"; return false; }
+  const pmx_call C{this, "surface locate", s};
+  if (nt < 1) return C.fail("surface points present but the background has no boundary trias");
+  // the overflow workspace: allocated once (the sequential mode grows it for its own pass)
+  if (!C.grow(d_blist, (size_t)nq) || !C.grow(d_olist, (size_t)nq) ||
+      !C.grow(d_bphi, (size_t)std::max<int64_t>(nq_bdy_ub, 1)) ||
+      (!d_ows.p && !C.grow(d_ows, (size_t)OVF_THREADS * 3 * OVF_CAP)))
+    return false;
   // tria hint grid: sized and allocated with the background
   // (pmx_ctx::size_tria_grid), zeroed and built at the head of the surface
   // path (off the main stream); none with point-map starts
-  if (!pointmap && hipMemsetAsync(d_tgrid.p, 0, sizeof(int) * (size_t)tcells, s) != hipSuccess) {
-    err = "tria hint grid memset";
-    return false;
-  }
   if (!pointmap) {
+    if (!C.hip(hipMemsetAsync(d_tgrid.p, 0, sizeof(int) * (size_t)tcells, s), "tria hint grid memset")) return false;
     int64_t nb = (nt + 255) / 256;
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_tria_hint_build, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(256), 0, s,
                        d_tris.p, d_xyz.p, nt, d_tgrid.p, tgd);
   }
   launch_bdy_walks(bdy_args(this, a, pointmap), d_ows.p, s, OVF_THREADS, false, pointmap);
-  return hipGetLastError() == hipSuccess;
-}
-
-// ---- PMX_RUN_SEQUENTIAL_SURFACE ---------------------------------------------
-//
-// The reference runs the surface queries one after the other
-// (src/interpmesh_pmmg.c:535-599): in the vertex loop's first-visit order
-// through the new tets, each PMMG_locatePointBdy starting from the previous
-// one's tria (ifoundTria, :529/:556), with mesh->base counting every locate
-// (volume and surface, :521, src/locate_pmmg.c:607/805) and the point flags
-// of the shadow tests kept from query to query (PMMG_locatePointInCone marks
-// the apex with the base and its scanned neighbours with the apex index, and
-// skips a neighbour already marked with it, src/locate_pmmg.c:219,247-249;
-// PMMG_locatePointInWedge marks an edge end, :318-323).  A query reads those
-// flags only through a wedge test (a walk that meets an already visited
-// tria, :640-660).  On the device:
-//  1. first-visit keys 4 k + l of every point (k_seq_keys), sorted: the visit
-//     order; a scan gives each located point its mesh->base and each
-//     surface point its position in the surface sequence;
-//  2. a speculative pass of every surface query (the step's walks) starting
-//     from the device-semantics result of its predecessor, with its
-//     reference base; it records whether the walk ran a wedge test;
-//  3. one wavefront replays the sequence (k_seq_resolve): a query whose
-//     speculative start is the true one (the previous query's true tria) and
-//     whose walk never met the shadow tests keeps its speculative result --
-//     it read no carried state; any other is run again by one lane on the
-//     reference's own state (tria flags vs base, point flags kept across
-//     queries), in order.  A replayed walk that ends stuck hands its point to
-//     the exhaustive scan (k_exh_bdy, one launch from the host) and the
-//     replay resumes after it.
-
-// the first visit of every new point by the reference's vertex loop: key
-// 4 k + l over the valid tets that hold it (atomicMin).  A lane skips the
-// vertices its left neighbour (the previous tet) holds: that tet's keys are
-// smaller, so the run's leftmost lane gives the minimum (as k_mark_new_tets)
-__global__ __launch_bounds__(256) void k_seq_keys(const int4 *__restrict__ tv, int64_t ne,
-                                                  unsigned *__restrict__ key) {
-  const int64_t st = (int64_t)gridDim.x * blockDim.x;
-  const int64_t nit = (ne + st - 1) / st;
-  const bool lane0 = (threadIdx.x & 63) == 0;
-  for (int64_t it = 0; it < nit; it++) {
-    const int64_t k = 1 + it * st + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int4 a = k <= ne ? tv[k] : make_int4(0, 0, 0, 0);
-    int4 u;
-    u.x = __shfl_up(a.x, 1, 64); u.y = __shfl_up(a.y, 1, 64);
-    u.z = __shfl_up(a.z, 1, 64); u.w = __shfl_up(a.w, 1, 64);
-    if (lane0 || u.x <= 0) u = make_int4(0, 0, 0, 0);
-    if (a.x <= 0) continue;
-    const int w[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-    for (int l = 0; l < 4; l++) {
-      const int q = w[l];
-      if (q != u.x && q != u.y && q != u.z && q != u.w) atomicMin(key + (q - 1), (unsigned)(4 * k + l));
-    }
-  }
-}
-// idx[i] = i; the speculative start (1) and base (0) of every point: a
-// surface point the loop never reaches (an orphan, located by a step without
-// the marks and reset afterwards) walks from tria 1
-__global__ __launch_bounds__(256) void k_seq_iota(int *__restrict__ idx, int *__restrict__ sstart,
-                                                  int *__restrict__ sbase, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    idx[i] = (int)i;
-    sstart[i] = 1;
-    sbase[i] = 0;
-  }
-}
-// per visit-order rank: located (a volume or surface point the loop reaches:
-// not NUL, not frozen) in the low word, surface in the high word
-__global__ __launch_bounds__(256) void k_seq_flags(const unsigned *__restrict__ skey, const int *__restrict__ sidx,
-                                                   const int8_t *__restrict__ kind, int64_t n,
-                                                   unsigned long long *__restrict__ val) {
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-    const int8_t kd = kind[sidx[r]];
-    const bool loc = skey[r] != 0xffffffffu && (kd == KIND_VOL || kd == KIND_BDY);
-    val[r] = (unsigned long long)(loc ? 1u : 0u) | ((unsigned long long)(loc && kd == KIND_BDY ? 1u : 0u) << 32);
-  }
-}
-// mesh->base of each located point (1 + the locates before it), the surface
-// and the volume sequences; their lengths into nseq[0] / nseq[1]
-__global__ __launch_bounds__(256) void k_seq_assign(const int *__restrict__ sidx,
-                                                    const unsigned long long *__restrict__ val,
-                                                    const unsigned long long *__restrict__ pre, int64_t n,
-                                                    int *__restrict__ base, int *__restrict__ seq,
-                                                    int *__restrict__ vseq, int *__restrict__ nseq) {
-  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-    const unsigned long long v = val[r], q = pre[r];
-    const unsigned located = (unsigned)(q & 0xffffffffull), bdy = (unsigned)(q >> 32);
-    if (v & 1ull) {
-      const int i = sidx[r];
-      base[i] = (int)located + 1;
-      if (v >> 32) seq[bdy] = i;
-      else vseq[located - bdy] = i;
-    }
-    if (r == n - 1) {
-      const unsigned long long e = q + v;
-      nseq[0] = (int)(e >> 32);
-      nseq[1] = (int)((e & 0xffffffffull) - (e >> 32));
-    }
-  }
-}
-// the speculative start of every surface query: its predecessor's tria from
-// the step's (device-semantics) pass; the first query starts at tria 1 (:529)
-__global__ __launch_bounds__(256) void k_seq_starts(const int *__restrict__ seq, const int *__restrict__ nseq,
-                                                    const int *__restrict__ elem, int *__restrict__ sstart) {
-  const int n = *nseq;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
-    sstart[seq[j]] = j ? elem[seq[j - 1]] : 1;
-}
-
-// the replay: one wavefront.  ctl = {next position, start tria of it (-1: the
-// tria of the previous query, written by the exhaustive scan), state (0 done,
-// 1 stuck: the host scans), stuck point}.  Tria / point flags through
-// agent-scope accesses (the lane re-reads what it wrote in earlier queries).
-// flags[j] (j < nmax) = surface position j must be looked at by the replay:
-// its speculative walk read carried state (a wedge / cone test) or started
-// from another tria than its predecessor's speculative result
-__global__ __launch_bounds__(256) void k_seq_sflags(const int *__restrict__ seq, const int *__restrict__ nseq_p,
-                                                    const int *__restrict__ sstart, const uint8_t *__restrict__ sw,
-                                                    const int *__restrict__ elem, int64_t nmax,
-                                                    uint8_t *__restrict__ flags) {
-  const int n = *nseq_p;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nmax; j += (int64_t)gridDim.x * blockDim.x) {
-    bool bad = false;
-    if (j < n) {
-      const int i = seq[j];
-      const int want = j == 0 ? 1 : elem[seq[j - 1]];
-      bad = sw[i] || sstart[i] != want;
-    }
-    flags[j] = bad ? 1 : 0;
-  }
+  return C.hip(hipGetLastError(), "launch");
 }
 
 // the replay, one lane, in visit order over the candidate positions (cand,
@@ -1356,198 +882,10 @@ __global__ __launch_bounds__(64) void k_seq_resolve(BdyArgs A, const int *__rest
   atomicAdd(nreplay, replays);
 }
 
-bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
-  const pmx_call C{this, "sequential replay", s};
-  seq_stats[0] = seq_stats[1] = seq_stats[2] = seq_stats[3] = 0;
-  if (!surf && !vol) return true;
-  if (!have_ntet) {
-    err = "PMX_RUN_SEQUENTIAL_*: the first-visit order needs the new tets (points view or pmx_upload_new_tets)";
-    return false;
-  }
-  if (nq < 1) return true;
-  if (!ensure_tets(s)) return false;
-  const int64_t n = nq;
-  size_t sort_b = 0, scan_b = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const unsigned *)nullptr, (unsigned *)nullptr,
-                                     (const int *)nullptr, (int *)nullptr, (int)n, 0, 32, s);
-  hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const unsigned long long *)nullptr,
-                                   (unsigned long long *)nullptr, (int)n, s);
-  if (!pmx_dgrow(this, d_sqkey, (size_t)(2 * n)) || !pmx_dgrow(this, d_sqidx, (size_t)(2 * n)) ||
-      !pmx_dgrow(this, d_sqval, (size_t)(2 * n)) || !pmx_dgrow(this, d_sqint, (size_t)(4 * n + 128)) ||
-      !pmx_dgrow(this, d_sqw, (size_t)n) || !pmx_dgrow(this, d_sqtmp, std::max(sort_b, scan_b)) ||
-      (surf && (!pmx_dgrow(this, d_sqtf, (size_t)(nt + 1)) || !pmx_dgrow(this, d_sqpf, (size_t)(np + 1)))) ||
-      (vol && !pmx_dgrow(this, d_sqtv, (size_t)(ne + 1))))
-    return false;
-  unsigned *key = d_sqkey.p, *key2 = d_sqkey.p + n;
-  int *idx = d_sqidx.p, *idx2 = d_sqidx.p + n;
-  unsigned long long *val = d_sqval.p, *pre = d_sqval.p + n;
-  int *sbase = d_sqint.p, *seq = d_sqint.p + n, *vseq = d_sqint.p + 2 * n, *sstart = d_sqint.p + 3 * n;
-  int *ctl = d_sqint.p + 4 * n;                  // [0..3] surface replay, [4..7] volume replay
-  int *nseq = ctl + 8;                           // [0] surface, [1] volume
-  unsigned *stk_count = (unsigned *)(ctl + 10), *nreplay = (unsigned *)(ctl + 11);   // [11] surface, [12] volume
-  int *stk_list = ctl + 13, *vstk_list = ctl + 14;
-  unsigned *vcounts = (unsigned *)(ctl + 32);   // the volume fallback's step counters (32 words)
-  int *vfound = ctl + 16, *vbestk = ctl + 17;
-  const unsigned nbt = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_ntet + 255) / 256, 8192));
-  const unsigned nbp = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192));
-  // 1. visit order, bases, sequences
-  if (!C.hip(hipMemsetAsync(key, 0xff, (size_t)n * sizeof(unsigned), s), "memset") ||
-      !C.hip(hipMemsetAsync(ctl, 0, 64 * sizeof(int), s), "memset"))
-    return false;
-  hipLaunchKernelGGL(k_seq_keys, dim3(nbt), dim3(256), 0, s, (const int4 *)d_ntetv.p, n_ntet, key);
-  hipLaunchKernelGGL(k_seq_iota, dim3(nbp), dim3(256), 0, s, idx, sstart, sbase, n);
-  if (!C.hip(hipcub::DeviceRadixSort::SortPairs(d_sqtmp.p, sort_b, (const unsigned *)key, key2, (const int *)idx, idx2,
-                                            (int)n, 0, 32, s), "sort"))
-    return false;
-  hipLaunchKernelGGL(k_seq_flags, dim3(nbp), dim3(256), 0, s, (const unsigned *)key2, (const int *)idx2,
-                     (const int8_t *)d_kind.p, n, val);
-  if (!C.hip(hipcub::DeviceScan::ExclusiveSum(d_sqtmp.p, scan_b, (const unsigned long long *)val, pre, (int)n, s),
-          "scan"))
-    return false;
-  hipLaunchKernelGGL(k_seq_assign, dim3(nbp), dim3(256), 0, s, (const int *)idx2, (const unsigned long long *)val,
-                     (const unsigned long long *)pre, n, sbase, seq, vseq, nseq);
-  if (surf && nq_bdy_ub > 0) {
-    // 2. the speculative surface pass
-    hipLaunchKernelGGL(k_seq_starts, dim3(nbp), dim3(256), 0, s, (const int *)seq, (const int *)nseq,
-                       (const int *)d_elem.p, sstart);
-    if (!C.hip(hipMemsetAsync(d_counts.p + 1, 0, 2 * sizeof(unsigned), s), "memset")) return false;
-    BdyArgs B = bdy_args(this, a);
-    B.seq_start = sstart;
-    B.seq_base = sbase;
-    B.seq_w = d_sqw.p;
-    // the overflow pass on hashed lists and 2x the threads (C3: 82-96 ms of
-    // long speculative walks on linear lists)
-    const int seq_ovf = 2 * OVF_THREADS;
-    const size_t ws_ints = (size_t)seq_ovf * GHS_SLOTS * 6;
-    if (!pmx_dgrow(this, d_ows, ws_ints) ||
-        !C.hip(hipMemsetAsync(d_ows.p, 0, ws_ints * sizeof(int), s), "memset"))
-      return false;
-    launch_bdy_walks(B, d_ows.p, s, seq_ovf, true);
-    // 3. the replay, on the reference's state
-    if (!C.hip(hipMemsetAsync(d_sqtf.p, 0, (size_t)(nt + 1) * sizeof(int), s), "memset") ||
-        !C.hip(hipMemsetAsync(d_sqpf.p, 0x80, (size_t)(np + 1) * sizeof(int), s), "memset"))
-      return false;
-    int hctl[4] = {0, 1, 0, 0};
-    if (!C.hip(hipMemcpyAsync(ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
-    // the replay's candidates, in visit order
-    {
-      size_t sel_b = 0;
-      hipcub::CountingInputIterator<int> it(0);
-      if (!C.hip(hipcub::DeviceSelect::Flagged(nullptr, sel_b, it, (const uint8_t *)nullptr, (int *)nullptr,
-                                            (int *)nullptr, (int)nq_bdy_ub, s),
-              "select") ||
-          !pmx_dgrow(this, d_sqflag, (size_t)nq_bdy_ub) || !pmx_dgrow(this, d_sqcand, (size_t)nq_bdy_ub + 1) ||
-          !pmx_dgrow(this, d_sqtmp, sel_b))
-        return false;
-      const unsigned nbs = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nq_bdy_ub + 255) / 256, 8192));
-      hipLaunchKernelGGL(k_seq_sflags, dim3(nbs), dim3(256), 0, s, (const int *)seq, (const int *)nseq,
-                         (const int *)sstart, (const uint8_t *)d_sqw.p, (const int *)d_elem.p, (int64_t)nq_bdy_ub,
-                         d_sqflag.p);
-      if (!C.hip(hipcub::DeviceSelect::Flagged(d_sqtmp.p, sel_b, it, (const uint8_t *)d_sqflag.p, d_sqcand.p + 1,
-                                            d_sqcand.p, (int)nq_bdy_ub, s),
-              "select"))
-        return false;
-    }
-    BdyArgs X = B;
-    X.stuck_list = stk_list;
-    X.stuck_count = stk_count;
-    for (;;) {
-      hipLaunchKernelGGL(k_seq_resolve, dim3(1), dim3(64), 0, s, B, (const int *)seq, (const int *)nseq,
-                         (const int *)sstart, (const uint8_t *)d_sqw.p, (const int *)sbase, d_sqtf.p, d_sqpf.p, ctl,
-                         stk_list, stk_count, nreplay, (const int *)(d_sqcand.p + 1), (const int *)d_sqcand.p);
-      if (!C.hip(hipMemcpyAsync(hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, s), "ctl") ||
-          !C.hip(hipStreamSynchronize(s), "sync"))
-        return false;
-      if (hctl[2] == 0) break;
-      // a replayed query ended stuck: the exhaustive scan of that one point
-      hipLaunchKernelGGL(k_exh_bdy, dim3(1), dim3(256), 0, s, X);
-      hctl[0] += 1;
-      hctl[1] = -1;
-      hctl[2] = 0;
-      if (!C.hip(hipMemcpyAsync(ctl, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
-    }
-  }
-  if (vol && nq_vol_ub > 0) {
-    // the volume: speculative pass from the predecessors' device results, then
-    // the replay on the reference's tet flags
-    hipLaunchKernelGGL(k_seq_starts, dim3(nbp), dim3(256), 0, s, (const int *)vseq, (const int *)(nseq + 1),
-                       (const int *)d_elem.p, sstart);
-    SeqVolArgs SV{vseq, nseq + 1, sstart, sbase, d_sqw.p, d_sqtv.p, ctl + 4, vstk_list, nreplay + 1, nullptr, nullptr};
-    // the overflow pass's hash tables: generation 0 = empty (positions start at 1)
-    if (!pmx_dgrow(this, d_sqows, seqv_ovf_ws_ints()) ||
-        !C.hip(hipMemsetAsync(d_sqows.p, 0, seqv_ovf_ws_ints() * sizeof(int), s), "memset"))
-      return false;
-    launch_seqv_spec(a, SV, nq_vol_ub, d_sqows.p, s);
-    // the replay's candidates: positions whose speculative start may be wrong,
-    // in visit order (DeviceSelect keeps the order)
-    {
-      size_t sel_b = 0;
-      hipcub::CountingInputIterator<int> it(0);
-      if (!C.hip(hipcub::DeviceSelect::Flagged(nullptr, sel_b, it, (const uint8_t *)nullptr, (int *)nullptr,
-                                            (int *)nullptr, (int)nq_vol_ub, s),
-              "select") ||
-          !pmx_dgrow(this, d_sqflag, (size_t)nq_vol_ub) || !pmx_dgrow(this, d_sqcand, (size_t)nq_vol_ub + 1) ||
-          !pmx_dgrow(this, d_sqtmp, sel_b))
-        return false;
-      launch_seqv_flags(a, SV, nq_vol_ub, d_sqflag.p, s);
-      if (!C.hip(hipcub::DeviceSelect::Flagged(d_sqtmp.p, sel_b, it, (const uint8_t *)d_sqflag.p, d_sqcand.p + 1,
-                                            d_sqcand.p, (int)nq_vol_ub, s),
-              "select"))
-        return false;
-      SV.ncand = d_sqcand.p;
-      SV.cand = d_sqcand.p + 1;
-    }
-    if (!C.hip(hipMemsetAsync(d_sqtv.p, 0, (size_t)(ne + 1) * sizeof(int), s), "memset")) return false;
-    int hctl[4] = {0, 1, 0, 0};
-    if (!C.hip(hipMemcpyAsync(ctl + 4, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
-    for (;;) {
-      launch_seqv_resolve(a, SV, s);
-      if (!C.hip(hipMemcpyAsync(hctl, ctl + 4, sizeof hctl, hipMemcpyDeviceToHost, s), "ctl") ||
-          !C.hip(hipStreamSynchronize(s), "sync"))
-        return false;
-      if (hctl[2] == 0) break;
-      // a replayed walk got stuck: k_fallback on that one point (its own
-      // counters: stuck count 1, no ties, barrier and error words zero)
-      const unsigned one = 1u;
-      const int imax = 0x7fffffff;
-      const unsigned long long umax = ~0ull;
-      if (!C.hip(hipMemsetAsync(vcounts, 0, 32 * sizeof(unsigned), s), "memset") ||
-          !C.hip(hipMemcpyAsync(vcounts, &one, sizeof one, hipMemcpyHostToDevice, s), "fallback") ||
-          !C.hip(hipMemcpyAsync(vfound, &imax, sizeof imax, hipMemcpyHostToDevice, s), "fallback") ||
-          !C.hip(hipMemcpyAsync(vbestk, &imax, sizeof imax, hipMemcpyHostToDevice, s), "fallback") ||
-          !C.hip(hipMemcpyAsync(val, &umax, sizeof umax, hipMemcpyHostToDevice, s), "fallback"))
-        return false;
-      VolArgs V = a;
-      V.stuck_list = vstk_list;
-      V.stuck_count = vcounts;
-      V.tie_count = vcounts + 3;
-      V.found = vfound;
-      V.bestk = vbestk;
-      V.best = val;
-      ExhArgs E{};
-      E.xyz = d_xyz.p; E.tets = d_tets.p; E.ne = ne; E.q = d_qxyz.p;
-      E.list = vstk_list; E.count = vcounts; E.found = vfound; E.best = val; E.bestk = vbestk;
-      E.spin_limit = 1L << 26;
-      launch_exhaustive(E, V, fallback_blocks, s);
-      if (!C.hip(hipStreamSynchronize(s), "sync")) return false;
-      unsigned derr = 0;
-      if (!C.hip(hipMemcpy(&derr, vcounts + PMX_CNT_ERR, sizeof derr, hipMemcpyDeviceToHost), "fallback")) return false;
-      if (derr) { err = "sequential replay: the one-point fallback's grid barrier timed out"; return false; }
-      hctl[0] += 1;
-      hctl[1] = -1;
-      hctl[2] = 0;
-      if (!C.hip(hipMemcpyAsync(ctl + 4, hctl, sizeof hctl, hipMemcpyHostToDevice, s), "ctl")) return false;
-    }
-  }
-  unsigned hr[2];
-  int hn[2];
-  if (!C.hip(hipMemcpyAsync(hr, nreplay, sizeof hr, hipMemcpyDeviceToHost, s), "stats") ||
-      !C.hip(hipMemcpyAsync(hn, nseq, sizeof hn, hipMemcpyDeviceToHost, s), "stats") ||
-      !C.hip(hipStreamSynchronize(s), "sync"))
-    return false;
-  seq_stats[0] = surf ? hr[0] : 0;
-  seq_stats[1] = surf ? (unsigned)hn[0] : 0;
-  seq_stats[2] = vol ? hr[1] : 0;
-  seq_stats[3] = vol ? (unsigned)hn[1] : 0;
-  return hipGetLastError() == hipSuccess;
+void launch_seq_resolve(const BdyArgs &B, const SeqBdyArgs &q, hipStream_t s) {
+  hipLaunchKernelGGL(k_seq_resolve, dim3(1), dim3(64), 0, s, B, q.seq, q.nseq, q.sstart, q.sw, q.sbase, q.tf, q.pf,
+                     q.ctl, q.stk_list, q.stk_count, q.nreplay, q.cand, q.ncand);
+}
+void launch_exh_bdy(const BdyArgs &B, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_exh_bdy, dim3((unsigned)blocks), dim3(256), 0, s, B);
 }

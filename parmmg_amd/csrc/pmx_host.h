@@ -123,6 +123,11 @@ struct pmx_call {
   bool hip(hipError_t e, const char *what) const {
     return e == hipSuccess || fail(std::string(what) + ": " + hipGetErrorString(e));
   }
+  // pmx_dgrow with the caller named: "who: hipMalloc: <HIP's error string>"
+  template <class T> bool grow(DevBuf<T> &b, size_t n) const {
+    const hipError_t e = b.grow(n, n);
+    return e == hipSuccess || hip(e, "hipMalloc");
+  }
   bool sync(const char *what) const {
     if (hipStreamSynchronize(s) != hipSuccess || hipGetLastError() != hipSuccess) return fail(what);
     return true;
@@ -141,28 +146,28 @@ struct pmx_call {
   template <class In, class Out>
   bool exclusive_sum(DevBuf<char> &tmp, In in, Out out, int64_t n, const char *what) const {
     size_t b = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, b, in, out, (int)n, s);
-    return pmx_dgrow(ctx, tmp, b) && ok(hipcub::DeviceScan::ExclusiveSum(tmp.p, b, in, out, (int)n, s), what);
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, in, out, (int)n, s);
+    return grow(tmp, b) && ok(hipcub::DeviceScan::ExclusiveSum(tmp.p, b, in, out, (int)n, s), what);
   }
   template <class K, class V>
   bool sort_pairs(DevBuf<char> &tmp, const K *kin, K *kout, const V *vin, V *vout, int64_t n, int bits,
                   const char *what) const {
     size_t b = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, (int)n, 0, bits, s);
-    return pmx_dgrow(ctx, tmp, b) &&
+    (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, (int)n, 0, bits, s);
+    return grow(tmp, b) &&
            ok(hipcub::DeviceRadixSort::SortPairs(tmp.p, b, kin, kout, vin, vout, (int)n, 0, bits, s), what);
   }
   template <class In, class Flag, class Out>
   bool select_flagged(DevBuf<char> &tmp, In in, Flag flag, Out out, unsigned *nsel, int64_t n, const char *what) const {
     size_t b = 0;
-    hipcub::DeviceSelect::Flagged(nullptr, b, in, flag, out, nsel, (int)n, s);
-    return pmx_dgrow(ctx, tmp, b) && ok(hipcub::DeviceSelect::Flagged(tmp.p, b, in, flag, out, nsel, (int)n, s), what);
+    (void)hipcub::DeviceSelect::Flagged(nullptr, b, in, flag, out, nsel, (int)n, s);
+    return grow(tmp, b) && ok(hipcub::DeviceSelect::Flagged(tmp.p, b, in, flag, out, nsel, (int)n, s), what);
   }
   template <class In, class Out, class Sel>
   bool select_if(DevBuf<char> &tmp, In in, Out out, unsigned *nsel, int64_t n, Sel sel, const char *what) const {
     size_t b = 0;
-    hipcub::DeviceSelect::If(nullptr, b, in, out, nsel, (int)n, sel, s);
-    return pmx_dgrow(ctx, tmp, b) && ok(hipcub::DeviceSelect::If(tmp.p, b, in, out, nsel, (int)n, sel, s), what);
+    (void)hipcub::DeviceSelect::If(nullptr, b, in, out, nsel, (int)n, sel, s);
+    return grow(tmp, b) && ok(hipcub::DeviceSelect::If(tmp.p, b, in, out, nsel, (int)n, sel, s), what);
   }
 };
 // in a function that returns 0 on failure: "who: x: <HIP's error string>"

@@ -167,15 +167,16 @@ struct pmx_ctx {
   DevBuf<int2> d_ctile;                 // classification tile counts
   DevBuf<uint4> d_vstat, d_bstat;       // per-wave walk statistics
   DevBuf<int> d_blist, d_olist, d_ows;
-  // PMX_RUN_SEQUENTIAL_SURFACE (pmx_bdy.hip seq_surface): visit keys / order,
-  // located / surface flags and their scan, bases | sequence | speculative
-  // starts | control words, wedge flags, cub scratch, the replay's tria and
-  // point flags; seq_stats = {replayed queries, surface sequence length}
+  // PMX_RUN_SEQUENTIAL_SURFACE / _VOLUME (pmx_seq.hip seq_replay): visit keys /
+  // order, located / surface flags and their scan, bases | surface sequence |
+  // volume sequence | speculative starts | control block, wedge / sure flags,
+  // cub scratch, the replays' tria, point and tet flags, the volume
+  // speculation's overflow workspace, the candidate flags and positions
   DevBuf<unsigned> d_sqkey;
   DevBuf<int> d_sqidx, d_sqint, d_sqtf, d_sqpf, d_sqtv, d_sqows;
   DevBuf<unsigned long long> d_sqval;
   DevBuf<uint8_t> d_sqw, d_sqflag;
-  DevBuf<int> d_sqcand;                 // [0] count, then the volume replay's candidate positions
+  DevBuf<int> d_sqcand;                 // [0] count, then a replay's candidate positions
   DevBuf<char> d_sqtmp;
   unsigned seq_stats[4] = {0, 0, 0, 0};   // surface replays / sequence, volume replays / sequence
   int64_t seq_stats_n = -1;             // -1: the last step was not sequential
@@ -328,26 +329,27 @@ struct pmx_ctx {
   // the orphan marks of the new tets on stream s: d_qmark[j] = 1 when a valid
   // new tet holds point j (the reference's vertex loop, src/interpmesh_pmmg.c:535-541)
   bool mark_new_tets(hipStream_t s);
-  // the fans by rotation (closed manifold surface, checked at the upload:
-  // fan_rot) or by a sort; force 1: the counting sort
+  // the node -> trias fans (pmx_fans.hip): by rotation (closed manifold
+  // surface, checked at the upload: fan_rot) or by a sort
   bool fan_rot = false;
   bool fan_rotation(hipStream_t s, unsigned *d_bad, bool check = false);
   bool check_fans(hipStream_t s);
-  // from d_tris, np, nt (pmx_bdy.hip); check: the rotation also re-counts every
-  // vertex's trias, the upload's fan check (a FRESH step redoes it)
+  // from d_tris, np, nt; check: the rotation also finds the vertices with
+  // more than one fan, the upload's fan check (a FRESH step redoes it)
   bool build_node_trias(hipStream_t s, bool check = false);
   // the new points: kinds, lists (pmx_capi.hip); marks: the orphan marks
   // (d_qmark) classify points in no valid new tet as KIND_ORPH
   // pointmap: also the start element of every compacted point from its
   // source vertex (d_qsrc through d_pmap into d_pstart)
   bool classify(hipStream_t s, bool marks = false, bool pointmap = false);
-  // pointmap: a.grid holds the start elements (no tria hint grid is built)
+  // the step's surface locate (pmx_bdy.hip); pointmap: a.grid holds the start
+  // elements (no tria hint grid is built)
   bool launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap = false);
+  bool size_tria_grid();                  // tgd, tcells, d_tgrid from the background's bbox and nt (pmx_bdy.hip)
   // PMX_RUN_SEQUENTIAL_SURFACE / _VOLUME after the step's passes, on stream s
-  // (synchronises the host: a replayed query that ends stuck is scanned by a
-  // launch of its own; pmx_bdy.hip)
+  // (synchronises the host: a replayed query that ends stuck is rescued by a
+  // launch of its own; pmx_seq.hip)
   bool seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol);
-  bool size_tria_grid();
   bool pack_new_tets();                   // the pending new tets: pack, send on `up`, residency build
   bool ensure_tets(hipStream_t s);        // d_ntetv valid for work on stream s
   bool fix_orphans();                     // the last step's rows of orphan points: untouched
@@ -358,6 +360,9 @@ struct pmx_ctx {
 };
 
 inline void pmx_set_error(pmx_ctx *ctx, std::string msg) { ctx->err = std::move(msg); }
+// the surface kernels' arguments for the step's points; pointmap: the start
+// trias of a.grid instead of the tria hint grid (pmx_bdy.hip)
+BdyArgs bdy_args(pmx_ctx *ctx, const VolArgs &a, bool pointmap = false);
 // the context's pinned staging arena, at least `bytes` (pmx_capi.hip)
 char *pmx_hstage(pmx_ctx *ctx, size_t bytes);
 // qualities dev[0..ne] (stream order) into the caller's array: stride 8

@@ -64,6 +64,42 @@ struct VolArgs {
                                 // 18 compact records whatever their far fields
 };
 
+// the surface kernels' arguments (pmx_bdy.hip; filled by bdy_args, pmx_internal.h)
+struct BdyArgs {
+  const double *xyz;        // old vertices, 24 B
+  const TriRec *tris;
+  const Pt4 *trn;
+  const int2 *ntrange;      // fan [lo, hi) in ntlist of vertex l of tria k, at 3 k + l
+  const int *ntlist;
+  const double *sol;
+  SolDesc sd;
+  const double *q;          // new points, dense x y z (0-based)
+  const int8_t *kind;
+  int64_t nq, nt;
+  double hausd;
+  const int *grid;     // tria hint grid (shares GridDesc with the tet grid); a
+                       // PMX_RUN_POINTMAP step: the start tria of every list entry
+  GridDesc g;
+  double *out;
+  uint8_t *wmask;
+  int *elem, *status, *steps, *start, *edge, *vertex;
+  Pt4 *bphi;           // (non-null, nlist entries) per entry of `list`: the 3 barycentrics the point's fields were
+                       // interpolated with, in the tria's vertex order (pmx_interp_more)
+  int *stuck_list;     // bdy exhaustive list
+  unsigned *stuck_count;
+  int *ovf_list;       // private-list overflow
+  unsigned *ovf_count;
+  const int *list;       // indices of the boundary points
+  int64_t nlist;         // upper bound (launch size); the step's count is *nlist_dev
+  const int *nlist_dev;
+  uint4 *wstats;         // per-wave walk statistics
+  // PMX_RUN_SEQUENTIAL_SURFACE's speculative pass: per point its start tria
+  // and mesh->base (null: the hint tria, ordinal + 1), and whether the walk
+  // ran a shadow-wedge test (the only path to the point flags)
+  const int *seq_start, *seq_base;
+  uint8_t *seq_w;
+};
+
 struct ExhArgs {
   const double *xyz;
   const TetRec *tets;
@@ -181,6 +217,37 @@ void launch_seqv_resolve(const VolArgs &a, const SeqVolArgs &s, hipStream_t st);
 // flags[j] (j < nmax) = position j of the volume sequence must be checked by
 // the replay: not sure, or its start is not its predecessor's speculative tet
 void launch_seqv_flags(const VolArgs &a, const SeqVolArgs &s, int64_t nmax, uint8_t *flags, hipStream_t st);
+// The surface walks (pmx_bdy.hip): k_locate_bdy, its private-list overflow
+// pass on ovf_threads threads -- linear lists in ows (OVF_THREADS threads'
+// worth, the step's) or, hashed, tables of GHS_WS_INTS zeroed ints per thread
+// (the sequential mode's speculative pass, whose walks from the predecessors'
+// trias overflow by the thousand) -- and the exhaustive scan of the stuck list
+#define OVF_THREADS (64 * 64)
+#define GHS_SLOTS 4096               // per hash table and thread; at most half of them used
+#define GHS_WS_INTS (GHS_SLOTS * 6)  // visited trias (int2) + point flags (int4)
+void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_threads = OVF_THREADS, bool hashed = false,
+                      bool pointmap = false);
+// k_exh_bdy on `blocks` workgroups, one stuck point each at a time
+void launch_exh_bdy(const BdyArgs &B, int blocks, hipStream_t s);
+// PMX_RUN_SEQUENTIAL_SURFACE's replay (k_seq_resolve, pmx_bdy.hip): the
+// surface sequence and its length on the device, each point's speculative
+// start, mesh->base and wedge flag, the reference's tria flags (nt + 1, base
+// compare) and point flags (np + 1, PF_INIT: still the incident-tria count
+// PMMG_precompute_nodeTrias left), the control words, the one-point stuck
+// list of a replayed walk that ends stuck, the replay count, the candidates
+#define PF_INIT ((int)0x80808080)
+struct SeqBdyArgs {
+  const int *seq, *nseq;
+  const int *sstart, *sbase;
+  const uint8_t *sw;
+  int *tf, *pf;
+  int *ctl;
+  int *stk_list;
+  unsigned *stk_count;
+  unsigned *nreplay;
+  const int *cand, *ncand;   // the positions the replay must look at (sorted)
+};
+void launch_seq_resolve(const BdyArgs &B, const SeqBdyArgs &q, hipStream_t s);
 // workgroups of k_fallback that can be co-resident with `share` other
 // launches of it on this device (0 on error)
 int fallback_coresident_blocks(int device, int share);

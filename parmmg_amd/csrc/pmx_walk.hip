@@ -667,7 +667,7 @@ void launch_walk(const VolArgs &a, hipStream_t s, bool pointmap) {
 // on that start only where several tets contain the point (ties), where the
 // walk gets stuck (status -1 instead of 1) or where it steps into a deleted
 // tet (it spins there until step > ne and returns the closest tet visited,
-// :809-811, :846-851).  pmx_bdy.hip's seq_replay sorts the points into the
+// :809-811, :846-851).  pmx_seq.hip's seq_replay sorts the points into the
 // vertex loop's order; here:
 //  * k_seqv_spec -- every volume point walks the reference's walk exactly
 //    (stable ascending-lambda order, first unvisited neighbour, closest

@@ -1,5 +1,5 @@
 """PMMG_precompute_nodeTrias (src/locate_pmmg.c:134-195) by rotation through
-the tria adjacency, the rule of k_fan_rotate (parmmg_amd/csrc/pmx_bdy.hip),
+the tria adjacency, the rule of k_fan_rotate (parmmg_amd/csrc/pmx_fans.hip),
 restated on the CPU: every (tria, corner) slot turns around its vertex
 through Mmg's adjt (edge i opposite vertex i) and puts its tria at its rank
 in the window of the fan's smallest tria.  The lists equal the reference's

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from helpers import bits_equal, compare_volume, cube_case, lin_field
+from helpers import bits_equal, compare_exact, compare_volume, cube_case, lin_field
 from oracle import oracle as O
 from parmmg_amd import _native as N
 from parmmg_amd import mesh as M
@@ -444,7 +444,7 @@ def _surface_run(tr, m, x, t, sols):
 
 @pytest.mark.parametrize("open_surface", [False, True])
 def test_fans_by_rotation_equal_sorted_fans(transfer, monkeypatch, open_surface):
-    """PMMG_precompute_nodeTrias two ways (pmx_bdy.hip): the fans walked
+    """PMMG_precompute_nodeTrias two ways (pmx_fans.hip): the fans walked
     through the tria adjacency (closed manifold surface, checked at the
     upload) and the sorted (vertex, tria) pairs (PMX_FAN_ROTATION=0, and
     whatever the upload's check refuses: here an edge without its neighbour
@@ -466,6 +466,38 @@ def test_fans_by_rotation_equal_sorted_fans(transfer, monkeypatch, open_surface)
     for u, w in zip(a[2], b[2]):
         assert np.array_equal(u.view(np.uint64), w.view(np.uint64))
     assert np.count_nonzero((t != 0) & (b[1] == 1)) > 0.9 * np.count_nonzero(t != 0)
+
+
+def test_fans_by_radix_sort_of_a_small_surface(transfer, monkeypatch):
+    """The fans' third builder: the radix sort of the (vertex, tria) pairs,
+    taken when the rotation is refused and np > 15 nt (a surface that is small
+    beside the volume).  The background keeps only the trias of the cube's
+    face z = 0 (an open surface: the upload's check refuses the rotation by
+    itself), the new surface points are those on that face.  Every point bit
+    for bit as the oracle in device semantics."""
+    m, x, t, sols = cube_case(32, metric="iso")
+    keep = np.nonzero(np.all(m.xyz[m.tria[1:], 2] == 0.0, axis=1))[0] + 1
+    nt = len(keep)
+    new = np.zeros(m.nt + 1, np.int64)
+    new[keep] = np.arange(1, nt + 1)
+    old = m.adjt[1:3 * m.nt + 1].reshape(m.nt, 3)[keep - 1].astype(np.int64)     # 3 k' + e'
+    adjt = np.zeros(3 * nt + 4, np.int32)
+    adjt[1:3 * nt + 1] = np.where(new[old // 3] > 0, 3 * new[old // 3] + old % 3, 0).ravel()
+    m = M.Mesh(m.xyz, m.tet, m.adja, np.concatenate([m.tria[:1], m.tria[keep]]), adjt, m.hausd)
+    on = ((t & M.TAG_BDY) == 0) | (x[:, 2] == 0.0)
+    x, t = np.ascontiguousarray(x[on]), np.ascontiguousarray(t[on])
+    assert (m.np, m.nt, len(x), np.count_nonzero(t)) == (35937, 2048, 33792, 1024)
+    assert m.np > 15 * m.nt                          # past the counting sort's range
+    monkeypatch.setenv("PMX_FAN_ROTATION", "0")
+    transfer.upload_background(m, sols, 0)
+    transfer.upload_points(x, t)
+    transfer.run(record_starts=True)
+    r = transfer.download()
+    starts = transfer.starts()
+    edge, vert = transfer.border()
+    outs, elem, st, _, e, v = O.Oracle(m).interp(x, t, sols, imet=0, fresh=True, start_vol=starts, start_bdy=starts)
+    assert np.all(st == 1)
+    compare_exact((r.sols, r.elem, r.status, edge, vert), (outs, elem, st, e, v), np.arange(len(x)), len(sols))
 
 
 

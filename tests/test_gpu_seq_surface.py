@@ -135,6 +135,24 @@ def test_seq_surface_stuck_replays(transfer):
     assert st["nreplay"] >= len(off)
 
 
+def test_seq_volume_stuck_replays(transfer):
+    """Four volume points 0.05 outside the cube: the oracle's sequential run
+    gives them status 0 (the exhaustive search's closest tet) and every other
+    volume point status 1.  Their replayed walks find no containing tet and
+    end stuck, so the volume replay hands each to the one-point fallback and
+    resumes after it."""
+    n = 6
+    m, x, t, sols = cube_case(n, metric="iso")
+    tets = M.new_point_tets(n, x, t)          # the vertex enumeration, before the points move
+    x = x.copy()
+    vol = np.nonzero(t == 0)[0]
+    pick = vol[::41][:4]
+    assert len(pick) == 4
+    x[pick, 0] = 1.05
+    st, _ = check_seq(transfer, m, x, t, sols, tets)
+    assert st["vol_nreplay"] >= 4
+
+
 def test_seq_surface_needs_new_tets(transfer):
     m, x, t, sols = cube_case(5, metric="iso")
     transfer.upload_background(m, sols, 0)

@@ -16,7 +16,8 @@ ALLOWED = {"pmx_capi.hip": {"pmx_device_alloc": {"hipMalloc(": 1, "hipFree(": 1}
 GONE = ["free_all", "sp_free", "dfree(", "MCK(", "struct Scratch"]
 # files whose host code checks every HIP call through the call helper
 # (pmx_host.h: pmx_call, PMX_CK): no comparison with hipSuccess by hand
-ON_CALL_HELPER = ["pmx_quality.hip", "pmx_lengths.hip", "pmx_graph.hip", "pmx_reduce.hip"]
+ON_CALL_HELPER = ["pmx_quality.hip", "pmx_lengths.hip", "pmx_graph.hip", "pmx_reduce.hip",
+                  "pmx_bdy.hip", "pmx_fans.hip", "pmx_seq.hip"]
 
 
 def _sources():
