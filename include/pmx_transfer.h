@@ -27,6 +27,12 @@
  *   PMMG_merge_grps (src/mergemesh_pmmg.c:967-1073)
  *                                          -> pmx_merge_groups / pmx_merge_fetch /
  *                                             pmx_merge_adopt
+ *   PMMG_set_color_tetra / PMMG_mark_interfacePoints /
+ *   PMMG_part_moveInterfaces / PMMG_part_getInterfaces
+ *       (src/moveinterfaces_pmmg.c:119-134, 1052-1090, 1306-1440, 1150-1212)
+ *                                          -> pmx_moveifc_begin / _get_colors /
+ *                                             _set_colors / _layer / _marks /
+ *                                             _part
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -338,7 +344,10 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * it (-1 before the first, after a refusal of the plan and after a release).
  * which = 16 / 17 / 18: the last pmx_merge_groups / pmx_merge_fetch /
  * pmx_merge_adopt (each -1 before its first call, after a refusal of the plan
- * and after a release). */
+ * and after a release).
+ * which = 19 / 20: the last pmx_moveifc_begin / the last pmx_moveifc_layer
+ * (first to last device operation of the call; -1 before the first call, after
+ * a refusal, after a release and once a background install dropped the state). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -841,6 +850,99 @@ int pmx_merge_maps(pmx_ctx *ctx, int32_t g, int *point_new, int *tet_new);
 int pmx_merge_adopt(pmx_ctx *ctx, int imet);
 /* Frees the plan's device memory (pmx_destroy does too). */
 int pmx_merge_release(pmx_ctx *ctx);
+
+/* Interface displacement of the uploaded (or adopted) group: the steps of the
+ * reference's default repartitioning mode between the merge and
+ * PMMG_fix_contiguity -- PMMG_set_color_tetra, PMMG_mark_interfacePoints and
+ * the layers of PMMG_part_moveInterfaces (src/moveinterfaces_pmmg.c:119-134,
+ * 1052-1090, 1306-1440) --, and PMMG_part_getInterfaces (:1150-1212) after the
+ * fix ("Interface displacement").  The marks, the
+ * per-point state and negrp equal the reference's sequential loops, blocked
+ * layers included.  The state lives on the device until pmx_moveifc_release,
+ * the next pmx_moveifc_begin or pmx_destroy; pmx_upload_background,
+ * pmx_promote_background and pmx_merge_adopt drop it, as they drop a split plan.
+ *
+ * The priority map: a colour is nprocs*igrp + iproc, its weight
+ * mapgrp[igrp + displsgrp[iproc]] (the old group's tet count before the merge,
+ * gathered over the ranks); the lighter colour wins, the first met among equal
+ * ones.  displsgrp: nprocs + 1 entries from 0; nold_grp: this rank's old
+ * groups, displsgrp[myrank + 1] - displsgrp[myrank]. */
+typedef struct {
+  int32_t nprocs, myrank, nold_grp;
+  const int *displsgrp, *mapgrp;
+} pmx_moveifc_map;
+
+/* One layer.  front: front points walked; touched: front points a neighbouring
+ * ball recoloured towards (the side fronts); recolor: recolourings, a tet
+ * that changes twice counts twice; next: points of the following front;
+ * blocked: 1 when a group would have passed below nemin, so that the layer
+ * ran as the reference's sequential loop on one lane; blocks: balls that loop
+ * abandoned; maxball: the longest ball walked to its end; seq_launches:
+ * launches of the sequential loop; overflow_ip: the point whose ball
+ * overflowed (0: none). */
+typedef struct {
+  int64_t front, touched, recolor, next, blocked, blocks, maxball, seq_launches, overflow_ip;
+} pmx_moveifc_stats;
+
+/* tet_group: ne ints, the old group of tet k at k-1 (pmx_merge_out.tet_group);
+ * NULL: the live merge plan's, read on the device (after pmx_merge_adopt).
+ * The marks become nprocs*tet_group + myrank, every point takes the lightest
+ * colour around it and the slot 4*tet + iloc it met it first at, the front is
+ * the points that met a lighter colour after their first slot, negrp[g] =
+ * mapgrp of the local group g and nemin[g] = min(6, negrp[g]/2 + 1).
+ * *nfront (may be NULL): the front points.  Returns 0 (pmx_last_error),
+ * *nfront untouched: no group uploaded; 4*ne >= 2^31; a deleted tet; a
+ * tet_group value outside 0..nold_grp-1; a colour that occurs with mapgrp <= 0
+ * (the reference asserts); displsgrp not ascending from 0 or disagreeing with
+ * nold_grp; tet_group NULL without a merge plan of ne tets.
+ * pmx_kernel_ms(ctx, 19): its device time. */
+int pmx_moveifc_begin(pmx_ctx *ctx, const int32_t *tet_group, const pmx_moveifc_map *map, int64_t *nfront);
+
+/* The two ends of the node-communicator exchange before a layer
+ * (src/moveinterfaces_pmmg.c:1369-1376, 1406-1413) for the points ip[0..n-1]
+ * (node2int_node_comm_index1): get delivers their colours (tmp), set writes
+ * the reduced ones and makes every listed point front, whether its colour
+ * changed or not.  A point is expected once; listed twice it keeps the colour
+ * of its last entry, as the reference's loop would.  The exchange and its
+ * reduction stay with the caller.
+ * Refused, nothing written: no displacement begun; a point outside 1..np; for
+ * set a colour of no group or of one with mapgrp <= 0. */
+int pmx_moveifc_get_colors(pmx_ctx *ctx, int64_t n, const int *ip, int *color);
+int pmx_moveifc_set_colors(pmx_ctx *ctx, int64_t n, const int *ip, const int *color);
+
+/* One pass of src/moveinterfaces_pmmg.c:1415-1438: the balls of the front
+ * points in ascending order, the side fronts, the next front.  seq_steps:
+ * steps (ball tets visited) per launch of the sequential loop, 0 = the default
+ * (65536).  st may be
+ * NULL.  A deliberate difference: a ball of more than MMG3D_LMAX - 2 = 10238
+ * tets makes the reference leave the layer half-way; here the call returns 0,
+ * names the point (pmx_last_error, st->overflow_ip) and the state stays as at
+ * the layer's start, so that the caller can take the CPU path.
+ * pmx_kernel_ms(ctx, 20): its device time. */
+int pmx_moveifc_layer(pmx_ctx *ctx, int64_t seq_steps, pmx_moveifc_stats *st);
+
+/* The marks (ne ints, tet k at k-1): the part pmx_fix_contiguity takes in its
+ * interface-displacement form. */
+int pmx_moveifc_marks(pmx_ctx *ctx, int32_t *mark);
+/* The per-point state (np ints each, point i at i-1; any may be NULL): the
+ * colour, the slot 4*tet + iloc (-1 both for a point in no tet) and 1 on the
+ * front. */
+int pmx_moveifc_points(pmx_ctx *ctx, int *tmp, int *s, int *front);
+/* negrp and nemin of the local groups (nold_grp ints each; either may be NULL). */
+int pmx_moveifc_groups(pmx_ctx *ctx, int *negrp, int *nemin);
+
+/* PMMG_part_getInterfaces: the partition the marks stand for.  mark: ne ints
+ * (after pmx_fix_contiguity), NULL = the device's.  PMX_GRPSPL_MMG_TARGET:
+ * part = mark / nprocs, *ngrp = nold_grp; a mark of another rank is refused
+ * (the reference asserts).  PMX_GRPSPL_DISTR_TARGET: the used colours numbered
+ * from 0, ranks visited from myrank round; ngrps_all: the old groups of every
+ * rank (nprocs ints, NULL = the map's).  part: ne ints, written on success. */
+#define PMX_GRPSPL_DISTR_TARGET 1
+#define PMX_GRPSPL_MMG_TARGET 2
+int pmx_moveifc_part(pmx_ctx *ctx, const int32_t *mark, int target, const int *ngrps_all, int32_t *part,
+                     int32_t *ngrp);
+/* Frees the displacement's device memory (pmx_destroy does too). */
+int pmx_moveifc_release(pmx_ctx *ctx);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

@@ -192,6 +192,20 @@ class MergeOut(C.Structure):
                                     "ext_face_items")]
 
 
+class MoveIfcMap(C.Structure):
+    """pmx_moveifc_map: the colours' priority map."""
+    _fields_ = [("nprocs", C.c_int32), ("myrank", C.c_int32), ("nold_grp", C.c_int32),
+                ("displsgrp", iptr), ("mapgrp", iptr)]
+
+
+class MoveIfcStats(C.Structure):
+    """pmx_moveifc_stats."""
+    _fields_ = [(n, i64) for n in ("front", "touched", "recolor", "next", "blocked", "blocks", "maxball",
+                                   "seq_launches", "overflow_ip")]
+
+
+GRPSPL_DISTR_TARGET, GRPSPL_MMG_TARGET = 1, 2
+
 INQUA, OUTQUA, LESQUA = 0, 1, 2
 
 
@@ -264,6 +278,15 @@ SIGNATURES = {
     "pmx_merge_maps": (C.c_int, [C.c_void_p, C.c_int32, iptr, iptr]),
     "pmx_merge_adopt": (C.c_int, [C.c_void_p, C.c_int]),
     "pmx_merge_release": (C.c_int, [C.c_void_p]),
+    "pmx_moveifc_begin": (C.c_int, [C.c_void_p, i32ptr, C.POINTER(MoveIfcMap), C.POINTER(i64)]),
+    "pmx_moveifc_get_colors": (C.c_int, [C.c_void_p, i64, iptr, iptr]),
+    "pmx_moveifc_set_colors": (C.c_int, [C.c_void_p, i64, iptr, iptr]),
+    "pmx_moveifc_layer": (C.c_int, [C.c_void_p, i64, C.POINTER(MoveIfcStats)]),
+    "pmx_moveifc_marks": (C.c_int, [C.c_void_p, i32ptr]),
+    "pmx_moveifc_points": (C.c_int, [C.c_void_p, iptr, iptr, iptr]),
+    "pmx_moveifc_groups": (C.c_int, [C.c_void_p, iptr, iptr]),
+    "pmx_moveifc_part": (C.c_int, [C.c_void_p, i32ptr, C.c_int, iptr, i32ptr, i32ptr]),
+    "pmx_moveifc_release": (C.c_int, [C.c_void_p]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

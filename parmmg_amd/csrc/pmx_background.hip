@@ -126,7 +126,7 @@ int env_sample_mode() {
 // again (a promotion keeps the one its residency build was made for).
 void begin_background(pmx_ctx *ctx, bool layout_env) {
   ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
-  ctx->have_pmap = ctx->split_valid = false;
+  ctx->have_pmap = ctx->split_valid = ctx->moveifc_valid = false;
   ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = ctx->bg_btv = false;
   ctx->stat_np = -1;
   ctx->eager_nch = 0;

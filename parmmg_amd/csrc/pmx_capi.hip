@@ -1261,6 +1261,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && (which == 12 || which == 13)) return pmx_contig_kernel_ms(ctx, which);
   if (ctx && (which == 14 || which == 15)) return pmx_split_kernel_ms(ctx, which);
   if (ctx && which >= 16 && which <= 18) return pmx_merge_kernel_ms(ctx, which);
+  if (ctx && (which == 19 || which == 20)) return pmx_moveifc_kernel_ms(ctx, which);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;
@@ -1426,4 +1427,5 @@ DevEvent *pmx_ctx::next_event_slot() {
 pmx_ctx::~pmx_ctx() {
   pmx_split_free(this);
   pmx_merge_free(this);
+  pmx_moveifc_free(this);
 }

@@ -238,6 +238,12 @@ struct pmx_ctx {
   // fetch / adopt
   struct pmx_merge_plan *merge = nullptr;
   double merge_plan_ms = -1.0, merge_fetch_ms = -1.0, merge_adopt_ms = -1.0;
+  // Interface displacement (pmx_moveifc_*, pmx_moveifc.hip): its state with
+  // the device buffers, valid until the next background upload, promotion or
+  // adoption; device times of the last begin / layer
+  struct pmx_moveifc_state *moveifc = nullptr;
+  bool moveifc_valid = false;
+  double moveifc_begin_ms = -1.0, moveifc_layer_ms = -1.0;
   int64_t stat_np = -1;                // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
@@ -304,7 +310,7 @@ struct pmx_ctx {
   std::vector<DevEvent> events;
   int ev_used = 0;
 
-  ~pmx_ctx();                           // the split plan (pmx_capi.hip); the members release themselves
+  ~pmx_ctx();                           // the split, merge and displacement plans (pmx_capi.hip); the members release themselves
   DevEvent *next_event_slot();          // nullptr + err on failure
   bool order_hint_samples(int64_t ne, int64_t nverts, hipStream_t s);
   // the background's record set, and the one the residency build prepares
@@ -471,6 +477,13 @@ void pmx_split_free(pmx_ctx *ctx);
 // plan and its buffers freed (pmx_merge.hip)
 double pmx_merge_kernel_ms(pmx_ctx *ctx, int which);
 void pmx_merge_free(pmx_ctx *ctx);
+// the live merge plan's tet_group on the device (ne ints, tet k at k - 1) and
+// its tet count; false: no plan (pmx_merge.hip)
+bool pmx_merge_tet_group(pmx_ctx *ctx, const int **tgrp, int64_t *ne);
+// pmx_kernel_ms(ctx, 19 / 20): the last displacement begin / layer; the state
+// and its buffers freed (pmx_moveifc.hip)
+double pmx_moveifc_kernel_ms(pmx_ctx *ctx, int which);
+void pmx_moveifc_free(pmx_ctx *ctx);
 // A group that is already on the device (connectivity tv: 1-based int4, slot 0
 // unused; xyz: 3 (np + 1) doubles; sol: (np + 1) max(S, 1) doubles, interleaved;
 // bounding box lo / hi) becomes the uploaded group, as pmx_upload_background

@@ -444,6 +444,14 @@ void pmx_merge_free(pmx_ctx *ctx) {
   delete P;
 }
 
+bool pmx_merge_tet_group(pmx_ctx *ctx, const int **tgrp, int64_t *ne) {
+  const pmx_merge_plan *P = ctx->merge;
+  if (!P || !P->tgrp.p) return false;
+  *tgrp = P->tgrp.p;
+  *ne = P->ne;
+  return true;
+}
+
 double pmx_merge_kernel_ms(pmx_ctx *ctx, int which) {
   return which == 16 ? ctx->merge_plan_ms : which == 17 ? ctx->merge_fetch_ms : ctx->merge_adopt_ms;
 }

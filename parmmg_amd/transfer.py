@@ -802,6 +802,124 @@ class Transfer:
         self._merge = None
         self._chk(self.lib.pmx_merge_release(self.ctx), "pmx_merge_release")
 
+    # ---- interface displacement ------------------------------------------------
+    def moveifc_begin(self, tet_group: np.ndarray | None, map: dict) -> int:
+        """PMMG_set_color_tetra + PMMG_mark_interfacePoints on the uploaded (or
+        adopted) group (pmx_moveifc_begin): the front points.  tet_group: (ne,)
+        old group per tet, None = the live merge plan's, read on the device.
+        map: nprocs, myrank, displsgrp (nprocs + 1,), mapgrp."""
+        ne = self.bg_ne
+        tg = None if tet_group is None else np.ascontiguousarray(tet_group, np.int32)
+        if tg is not None and tg.shape != (ne,):
+            raise ValueError(f"tet_group has shape {tg.shape}, the group has {ne} tets")
+        nprocs, myrank = int(map.get("nprocs", 1)), int(map.get("myrank", 0))
+        displs = np.ascontiguousarray(map["displsgrp"], np.int32)
+        mapgrp = np.ascontiguousarray(map["mapgrp"], np.int32)
+        if displs.shape != (nprocs + 1,) or not 0 <= myrank < nprocs:
+            raise ValueError("displsgrp wants nprocs + 1 entries, myrank lies in 0..nprocs-1")
+        if len(mapgrp) != int(displs[-1]):
+            raise ValueError("mapgrp wants displsgrp[nprocs] entries")
+        mp = N.MoveIfcMap(nprocs, myrank, int(map.get("nold_grp", displs[myrank + 1] - displs[myrank])),
+                          _ip(displs), _ip(mapgrp) if mapgrp.size else None)
+        nf = C.c_int64(0)
+        self._moveifc = None
+        self._chk(self.lib.pmx_moveifc_begin(self.ctx, tg.ctypes.data_as(N.i32ptr) if tg is not None else None,
+                                             C.byref(mp), C.byref(nf)), "pmx_moveifc_begin")
+        self._moveifc = {"nold_grp": mp.nold_grp, "nprocs": nprocs, "myrank": myrank, "ne": ne, "np": self.bg_np}
+        return nf.value
+
+    def _moveifc_state(self) -> dict:
+        return getattr(self, "_moveifc", None) or {"nold_grp": 0, "nprocs": 1, "myrank": 0, "ne": self.bg_ne,
+                                                   "np": self.bg_np}
+
+    def moveifc_colors(self, ip: np.ndarray) -> np.ndarray:
+        """The colours (tmp) of the listed 1-based points (pmx_moveifc_get_colors)."""
+        p = np.ascontiguousarray(ip, np.int32)
+        col = np.zeros(len(p), np.int32)
+        self._chk(self.lib.pmx_moveifc_get_colors(self.ctx, len(p), _ip(p) if p.size else None,
+                                                  _ip(col) if p.size else None), "pmx_moveifc_get_colors")
+        return col
+
+    def moveifc_set_colors(self, ip: np.ndarray, color: np.ndarray):
+        """The listed points take the colours and join the front
+        (pmx_moveifc_set_colors)."""
+        p = np.ascontiguousarray(ip, np.int32)
+        col = np.ascontiguousarray(color, np.int32)
+        if p.shape != col.shape:
+            raise ValueError("ip and color differ in length")
+        self._chk(self.lib.pmx_moveifc_set_colors(self.ctx, len(p), _ip(p) if p.size else None,
+                                                  _ip(col) if p.size else None), "pmx_moveifc_set_colors")
+
+    def moveifc_layer(self, seq_steps: int = 0) -> dict:
+        """One layer of PMMG_part_moveInterfaces (pmx_moveifc_layer): its stats
+        as a dict.  A ball overflow raises; the state is the layer's start."""
+        st = N.MoveIfcStats()
+        self._moveifc_last = st
+        self._chk(self.lib.pmx_moveifc_layer(self.ctx, seq_steps, C.byref(st)), "pmx_moveifc_layer")
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    def moveifc_marks(self) -> np.ndarray:
+        """The tet marks (ne,), the input of fix_contiguity (pmx_moveifc_marks)."""
+        mk = np.zeros(self._moveifc_state()["ne"], np.int32)
+        self._chk(self.lib.pmx_moveifc_marks(self.ctx, mk.ctypes.data_as(N.i32ptr) if mk.size else
+                                             (C.c_int32 * 1)()), "pmx_moveifc_marks")
+        return mk
+
+    def moveifc_points(self):
+        """(tmp, s, front), (np,) each: the colour, the slot 4*tet + iloc and
+        the front flag of every point (pmx_moveifc_points)."""
+        n = self._moveifc_state()["np"]
+        tmp, s, fr = (np.zeros(n, np.int32) for _ in range(3))
+        self._chk(self.lib.pmx_moveifc_points(self.ctx, _ip(tmp) if n else None, _ip(s) if n else None,
+                                              _ip(fr) if n else None), "pmx_moveifc_points")
+        return tmp, s, fr
+
+    def moveifc_groups(self):
+        """(negrp, nemin) of the local groups (pmx_moveifc_groups)."""
+        n = self._moveifc_state()["nold_grp"]
+        a, b = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self._chk(self.lib.pmx_moveifc_groups(self.ctx, _ip(a), _ip(b)), "pmx_moveifc_groups")
+        return a[:n], b[:n]
+
+    def moveifc_part(self, mark: np.ndarray | None = None, target: int = N.GRPSPL_MMG_TARGET, ngrps_all=None):
+        """PMMG_part_getInterfaces (pmx_moveifc_part): (part (ne,), ngrp).
+        mark: the marks after fix_contiguity, None = the device's."""
+        ne = self._moveifc_state()["ne"]
+        mk = None if mark is None else np.ascontiguousarray(mark, np.int32)
+        if mk is not None and mk.shape != (ne,):
+            raise ValueError(f"mark has shape {mk.shape}, the group has {ne} tets")
+        ng = None if ngrps_all is None else np.ascontiguousarray(ngrps_all, np.int32)
+        if ng is not None and len(ng) != self._moveifc_state()["nprocs"]:
+            raise ValueError("ngrps_all wants nprocs entries")
+        part = np.zeros(max(ne, 1), np.int32)
+        n = C.c_int32(0)
+        self._chk(self.lib.pmx_moveifc_part(self.ctx, mk.ctypes.data_as(N.i32ptr) if mk is not None and ne else None,
+                                            target, _ip(ng) if ng is not None else None,
+                                            part.ctypes.data_as(N.i32ptr), C.byref(n)), "pmx_moveifc_part")
+        return part[:ne], n.value
+
+    def moveifc_release(self):
+        """Free the displacement's device memory (pmx_moveifc_release)."""
+        self._moveifc = None
+        self._chk(self.lib.pmx_moveifc_release(self.ctx), "pmx_moveifc_release")
+
+    def move_interfaces(self, tet_group, map: dict, nlayers: int = 2, exchange=None, node_points=None):
+        """PMMG_part_moveInterfaces: begin and nlayers layers.  exchange(colors)
+        -> colors is called before every layer with the colours of node_points
+        (the group's node-communicator points, 1-based) and returns the
+        reduced ones; it stands for the ranks' MPI exchange.  Returns (marks,
+        [stats of each layer]); stats[0]["nfront"] is begin's front."""
+        nfront = self.moveifc_begin(tet_group, map)
+        pts = None if node_points is None else np.ascontiguousarray(node_points, np.int32)
+        stats = []
+        for _ in range(nlayers):
+            if exchange is not None and pts is not None:
+                self.moveifc_set_colors(pts, exchange(self.moveifc_colors(pts)))
+            stats.append(self.moveifc_layer())
+        if stats:
+            stats[0]["nfront"] = nfront
+        return self.moveifc_marks(), stats
+
     def upload_new_tets(self, tets: np.ndarray):
         """The new mesh's tets, (ne+1, 4) with 0-based point indices (v[0] < 0:
         deleted), for pmx_promote_background / pmx_new_mesh_qual."""
