@@ -431,18 +431,17 @@ int pmx_upload_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol,
 }
 
 // The last step's points, results and new tets become the background (device
-// residency across ParMmg iterations, pmx_capi.hip): only the boundary trias
+// residency across ParMmg iterations, pmx_points.hip): only the boundary trias
 // and the rows the step did not write come from the host.
 
 int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const pmx_sol_view *sols) {
   if (!ctx) return 0;
   const pmx_call C{ctx, "pmx_promote_background", ctx->stream};
   if (!m) return C.fail("null mesh");
-  if (!ctx->ran || !ctx->have_pts || ctx->out_n != ctx->nq || ctx->out_S != ctx->sd.S)
-    return C.fail("no step has run on the current uploads");
-  if (!ctx->have_ntet) return C.fail("upload the new tets first");
+  if (!ctx->stepped() || ctx->out_S != ctx->sd.S) return C.fail("no step has run on the current uploads");
+  if (!ctx->ntets.have) return C.fail("upload the new tets first");
   if (ctx->pts_first != 1) return C.fail("the points view must start at 1 (Mmg numbering)");
-  const int64_t n = ctx->nq, ne = ctx->n_ntet, nt = m->nt;
+  const int64_t n = ctx->nq, ne = ctx->ntets.n, nt = m->nt;
   if (m->np != n || m->ne != ne || n < 1) return C.fail("mesh sizes differ from the uploaded points / new tets");
   if (nt < 0 || (nt > 0 && (!m->tria_v || !m->adjt || m->tria_stride < 12)))
     return C.fail("nt > 0 requires tria_v and adjt");
@@ -470,7 +469,7 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   hipSetDevice(ctx->device);
   Trace tr("promote");
   hipStream_t st = ctx->stream;
-  if (!ctx->fix_orphans() || !ctx->ensure_tets(st)) return 0;
+  if (!ctx->ntets.fix_orphans() || !ctx->ntets.ensure_tets(st)) return 0;
   PMX_CK(C, hipStreamSynchronize(st));
   if (!ctx->check_device_errors()) return 0;
   tr.mark("sync");
@@ -532,17 +531,16 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   // from the caller's Mmg adjacency (mesh->adja after remeshing) or from the
   // device's face matching (a residency build still running is then left to
   // finish behind ev_adja: its result is dropped)
-  const bool prepared = ctx->next_topo && !m->adja;
-  ctx->next_topo = false;
+  const bool prepared = ctx->ntets.take_next(!m->adja);
   if (prepared) {
-    PMX_CK(C, hipEventSynchronize(ctx->ev_topo));
+    PMX_CK(C, hipEventSynchronize(ctx->ntets.ev_topo));
     tr.mark("wait topo");
     std::swap(ctx->d_tets, ctx->d_tets_next);
     std::swap(ctx->d_wrec, ctx->d_wrec_next);
     std::swap(ctx->d_tets_s, ctx->d_tets_s_next);
     ctx->h_nbad.p[PMX_H_NONMANIFOLD] = ctx->h_nbad.p[PMX_H_NONMANIFOLD_NEXT];
     ctx->h_nbad.p[PMX_H_FAR] = ctx->h_nbad.p[PMX_H_FAR_NEXT];
-  } else if (!ctx->build_records(ctx->d_ntetv.p, m->adja, ne, n, ctx->records_current(), st)) {
+  } else if (!ctx->build_records(ctx->ntets.d_v.p, m->adja, ne, n, ctx->records_current(), st)) {
     return 0;
   }
   tr.mark("tet records");
@@ -550,7 +548,8 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
   if (!finish_background(C, {n, ne, nt, m->hausd, ctx->qlo, ctx->qhi, &htr, false, true, nullptr}, tr)) return 0;
   ctx->have_ptag = tags;
   // the points and the results were consumed: the next step needs new points
-  ctx->have_pts = ctx->ran = ctx->have_ntet = false;
+  ctx->have_pts = ctx->ran = false;
+  ctx->ntets.consumed();
   return 1;
 }
 

@@ -283,12 +283,12 @@ __global__ __launch_bounds__(256) void k_copy_required(const uint16_t *__restric
 extern "C" int pmx_copy_required(pmx_ctx *ctx, const int *permNodGlob, int copy_metric) {
   if (!ctx) return 0;
   hipSetDevice(ctx->device);
-  if (!ctx->ran || !ctx->have_pts || ctx->out_n != ctx->nq || ctx->out_S != ctx->sd.S) {
+  if (!ctx->stepped() || ctx->out_S != ctx->sd.S) {
     ctx->err = "pmx_copy_required: no step has run on the current uploads";
     return 0;
   }
   if (!ctx->have_ptag) { ctx->err = "pmx_copy_required: the background's point tags are not on the device"; return 0; }
-  if (!ctx->fix_orphans()) return 0;
+  if (!ctx->ntets.fix_orphans()) return 0;
   const int64_t np = ctx->np;
   hipStream_t s = ctx->stream;
   if (permNodGlob) {

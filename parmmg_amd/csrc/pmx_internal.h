@@ -11,6 +11,7 @@
 #include "pmx_transfer.h"
 #include "pmx_kernels.h"
 #include "pmx_host.h"
+#include "pmx_hostpool.h"
 
 // hint grid from every 4th tet: 1/4 of the stores and of the tet bytes of a
 // full build, at ~0.5 extra walk step (r01 measurements)
@@ -50,6 +51,72 @@ struct RecordSet {
   DevBuf<WRec> *wrec;
   DevBuf<int4> *sample;
   int d_far, h_nonmanifold, h_far;
+};
+
+// The new mesh's tets on the device and the orphan reset that depends on
+// them: one owner.  Other files read have / n / d_v and call the functions;
+// only pmx_points.hip assigns a member.
+//
+//   the tets   none            !have
+//              view kept       have, from_view, pending: `view` names the caller's rows, nothing is packed
+//              DMA in flight   have, inflight: packed into h, the copies (and marks) issued on `up`, ev recorded
+//              on the device   have, !pending, !inflight
+//   the marks  valid or not    marks: d_mark[j] = 1 where a valid current tet holds point j
+//   the rows   reset or not    rows_reset: the last step's rows of orphan points are "never visited" again
+//   next       none, building  next_topo: the next background's records being built from the tets on `topo`
+//
+//   transition          called by                       the tets                marks      rows
+//   points_begin        pmx_upload_points, first        none, drained; next dropped  not valid  reset
+//   view_kept           pmx_upload_points, last         view kept (none without tets)
+//   pack_new_tets       the end of the view's first     DMA in flight; next     valid      .
+//                       step; ensure_tets before it     building with residency
+//   replace             pmx_upload_new_tets             on the device; next     valid if   not reset if a
+//                                                       dropped                 from_view  step has run
+//   step_marks          a FRESH step with tets          DMA in flight           (being redone on `up`)
+//   step_done(true)     ... its end                     .                       valid      reset: never located
+//   step_done(false)    the end of any other step       .                       .          not reset
+//   fix_orphans         every consumer of results       .                       .          reset
+//   drain               points_begin, replace           in flight -> on the device
+//   drop_next           points_begin, replace           .                       next: none
+//   take_next           pmx_promote_background          .                       next: none (swapped in when wanted)
+//   consumed            ... its end                     none
+struct NewTets {
+  pmx_ctx *const ctx;
+  bool have = false;                    // there are new tets for the current points
+  int64_t n = 0;                        // ne of them; records 1..n, vertex = points-view index - first + 1
+  bool from_view = false;               // the points view carried them (orphans exist by definition)
+  bool pending = false, inflight = false;
+  bool marks = false, rows_reset = true;
+  bool next_topo = false;
+  pmx_points_view view{};
+  DevBuf<int4> d_v;                     // the tets, 1-based, slot 0 unused
+  DevBuf<uint8_t> d_mark;               // orphan marks, one byte per point
+  PinBuf<char> h;                       // pinned copy of the tets (int4, 0 = deleted); not the shared arena:
+                                        // it outlives the step (a strided quality output reads validity there)
+  DevEvent ev, ev_topo;                 // the DMA and marks on `up`; the residency build on `topo`
+  unsigned const_bit = 0;               // wmask bit of the last step's constant-size metric (kept by the reset)
+
+  explicit NewTets(pmx_ctx *c) : ctx(c) {}
+  bool points_begin();
+  void view_kept(const pmx_points_view &pv, int64_t ntet);
+  // the pending tets: validated, packed, sent on `up` in chunks, marked there;
+  // with residency the next background's records follow on `topo`
+  bool pack_new_tets();
+  bool replace(const int *tetra_v, int64_t tetra_stride, int64_t ne);
+  bool step_marks(hipStream_t st);      // the marks again on `up`, forked from st (which waits for ev later)
+  void step_done(bool marks_in_step, unsigned step_const_bit);
+  bool drain();                         // wait for ev on the host
+  bool drop_next();                     // wait for `topo` on the host
+  bool take_next(bool wanted);          // true: the prepared records are to be swapped in (after ev_topo)
+  void consumed();                      // a promotion took them: none
+  bool ensure_tets(hipStream_t s);      // d_v valid for work on stream s (packs a pending view)
+  // the marks from d_v[1..ne] on stream s: d_mark[j] = 1 when a valid new tet
+  // holds point j (the reference's vertex loop, src/interpmesh_pmmg.c:535-541)
+  bool mark_new_tets(int64_t ne, hipStream_t s);
+  // the last step located every live point; its rows of orphan points go back
+  // to untouched on the context's stream, before any consumer reads them
+  bool fix_orphans();
+  int4 *grow_htets(int64_t ne);         // h for ne + 1 records (ev already waited for)
 };
 
 struct pmx_ctx {
@@ -136,6 +203,9 @@ struct pmx_ctx {
   int64_t nq_vol_ub = 0, nq_bdy_ub = 0;
   int out_S = -1;                       // solution width the results were computed for
   int64_t out_n = -1;                   // point count the results were computed for
+  // a step has run on the current points (each caller adds have_bg and
+  // out_S == sd.S where it needs them)
+  bool stepped() const { return ran && have_pts && out_n == nq; }
   DevBuf<int8_t> d_kind;
   DevBuf<uint8_t> d_wmask;
   DevBuf<double> d_out;
@@ -157,7 +227,6 @@ struct pmx_ctx {
   std::vector<DevEvent> more_ev;
   int more_ev_used = 0;
   DevBuf<double> d_qxyz;                // new points as uploaded (dense xyz)
-  DevBuf<uint8_t> d_qmark;              // orphan marks (points of valid new tets), uploaded when needed
   DevBuf<int> d_nsel;                   // compaction counts: volume, surface
   // the new points' source vertices (pmx_upload_point_sources; dense, entry
   // j = view index first + j) and, of a PMX_RUN_POINTMAP step, the resolved
@@ -251,9 +320,6 @@ struct pmx_ctx {
   DevBuf<unsigned long long> d_pkey;    // prilen: excluded parallel edges (sorted keys)
   DevBuf<uint8_t> d_ppt;
   DevBuf<int2> d_pedge;                 // prilen: owned parallel edges (step 1)
-  DevBuf<int4> d_ntetv;                 // the new tets (pmx_upload_new_tets), 1-based
-  bool have_ntet = false;               //   vertex = points-view index - first + 1
-  int64_t n_ntet = 0;
   double qlo[3]{}, qhi[3]{};            // bbox of the uploaded new points
   // device adjacency (pmx_topo.hip), reused buffers.  d_adja and the face
   // matching's scratch below are build_records' alone: one scratch shared by
@@ -272,8 +338,6 @@ struct pmx_ctx {
   // from the new tets on the `topo` stream while the current step runs
   bool residency = false;
   hipStream_t topo = nullptr;
-  DevEvent ev_topo;
-  bool next_topo = false;               // d_tets_next / d_tets_s_next are being built
   DevBuf<TetRec> d_tets_next;
   DevBuf<WRec> d_wrec_next;
   DevBuf<int4> d_tets_s_next;
@@ -282,21 +346,10 @@ struct pmx_ctx {
   bool have_qtag = false;               // raw tags of the new points
   DevBuf<uint16_t> d_qtag;
   int64_t pts_first = 0;                // points view's first index
-  // the new tets of the points view: packed (validated, orphan marks) and
-  // sent by the first pmx_run after the upload, once its step is enqueued --
-  // their DMA on `up` overlaps the step and the results' download (the step
-  // itself never reads them); consumers wait for ev_tets (ensure_tets)
+  // the new tets' DMA and their orphan marks run on `up`, beside the step and
+  // the results' download; the new tets themselves are `ntets`
   hipStream_t up = nullptr;
-  DevEvent ev_tets;
-  PinBuf<char> h_tets;                  // pinned copy of the current new tets (int4, 0 = deleted); not the
-                                        // shared arena: it outlives the step (qualities' validity)
-  bool tets_pending = false;            // view kept, not packed yet
-  bool view_tets = false;               // the points view carried new tets (orphans exist by definition)
-  bool tets_inflight = false;           // DMA issued on `up`, ev_tets recorded
-  pmx_points_view tview{};
-  bool orph_marks = false;              // d_qmark holds the device's marks of the packed new tets
-  bool orph_fixed = true;               // the last step's orphan rows reset (fix_orphans)
-  unsigned last_const_bit = 0;          // wmask bit of the last step's constant-size metric
+  NewTets ntets{this};
   // PMX_RUN_EAGER_DOWNLOAD: the last step's fields (n * S doubles) and write
   // masks (n bytes) copied into h_out as soon as the step ends, in eager_nch
   // chunks (ev_eg); 0 = no such copy, or the results changed since
@@ -332,9 +385,6 @@ struct pmx_ctx {
   // (face matching + records when the device built the adjacency, compact
   // records, owner sample), again on stream s (pmx_background.hip)
   bool rederive(hipStream_t s);
-  // the orphan marks of the new tets on stream s: d_qmark[j] = 1 when a valid
-  // new tet holds point j (the reference's vertex loop, src/interpmesh_pmmg.c:535-541)
-  bool mark_new_tets(hipStream_t s);
   // the node -> trias fans (pmx_fans.hip): by rotation (closed manifold
   // surface, checked at the upload: fan_rot) or by a sort
   bool fan_rot = false;
@@ -343,8 +393,8 @@ struct pmx_ctx {
   // from d_tris, np, nt; check: the rotation also finds the vertices with
   // more than one fan, the upload's fan check (a FRESH step redoes it)
   bool build_node_trias(hipStream_t s, bool check = false);
-  // the new points: kinds, lists (pmx_capi.hip); marks: the orphan marks
-  // (d_qmark) classify points in no valid new tet as KIND_ORPH
+  // the new points: kinds, lists (pmx_points.hip); marks: the orphan marks
+  // (ntets.d_mark) classify points in no valid new tet as KIND_ORPH
   // pointmap: also the start element of every compacted point from its
   // source vertex (d_qsrc through d_pmap into d_pstart)
   bool classify(hipStream_t s, bool marks = false, bool pointmap = false);
@@ -356,11 +406,7 @@ struct pmx_ctx {
   // (synchronises the host: a replayed query that ends stuck is rescued by a
   // launch of its own; pmx_seq.hip)
   bool seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol);
-  bool pack_new_tets();                   // the pending new tets: pack, send on `up`, residency build
-  bool ensure_tets(hipStream_t s);        // d_ntetv valid for work on stream s
-  bool fix_orphans();                     // the last step's rows of orphan points: untouched
   bool eager_download();                  // issue the eager copies of the step just enqueued
-  int4 *grow_htets(int64_t ne);           // h_tets for ne + 1 records (ev_tets already waited)
   // device error word of the last step (after a stream sync): 0 = none
   bool check_device_errors();
 };
@@ -369,38 +415,16 @@ inline void pmx_set_error(pmx_ctx *ctx, std::string msg) { ctx->err = std::move(
 // the surface kernels' arguments for the step's points; pointmap: the start
 // trias of a.grid instead of the tria hint grid (pmx_bdy.hip)
 BdyArgs bdy_args(pmx_ctx *ctx, const VolArgs &a, bool pointmap = false);
-// the context's pinned staging arena, at least `bytes` (pmx_capi.hip)
+// the context's pinned staging arena, at least `bytes`, once the context's
+// stream has drained (pmx_capi.hip)
 char *pmx_hstage(pmx_ctx *ctx, size_t bytes);
 // qualities dev[0..ne] (stream order) into the caller's array: stride 8
 // (dense) writes qual[0..ne] with qual[0] = 0; any other stride (bytes, an
 // AoS field such as &MMG5_Tetra[0].qual) writes only the tets that are valid
-// in h_tets (deleted tets keep their value, as MMG3D_tetraQual skips
+// in ntets.h (deleted tets keep their value, as MMG3D_tetraQual skips
 // !MG_EOK).  Chunked through the pinned arena, each chunk's host scatter
-// overlapping the next one's DMA (pmx_capi.hip).
+// overlapping the next one's DMA (pmx_results.hip).
 bool pmx_download_qual(pmx_ctx *ctx, const double *dev, int64_t ne, double *qual, int64_t stride);
-// f(i0, i1) over [lo, hi) on the host pool (pmx_capi.hip)
-void pmx_par_for(int64_t lo, int64_t hi, const std::function<void(int64_t, int64_t)> &f);
-// the host pool itself (pmx_capi.hip): its thread count, the range size below
-// which a pass stays serial, job(0..n-1) over the workers and the caller
-unsigned pmx_host_threads();
-int64_t pmx_host_threads_min();
-void pmx_host_pool_run(const std::function<void(int)> &job, int n);
-// f(chunk, lo, hi) over C contiguous chunks of [lo, hi); returns C
-template <class F> static int par_chunks(int64_t lo, int64_t hi, F f) {
-  const int64_t n = hi - lo;
-  const int C = (pmx_host_threads() <= 1 || n < pmx_host_threads_min()) ? 1 : (int)pmx_host_threads();
-  if (C == 1) { f(0, lo, hi); return 1; }
-  const int64_t chunk = (n + C - 1) / C;
-  const std::function<void(int)> job = [&](int i) {
-    const int64_t a = lo + (int64_t)i * chunk, b = std::min(hi, a + chunk);
-    f(i, a, std::max(a, b));
-  };
-  pmx_host_pool_run(job, C);
-  return C;
-}
-template <class F> static void par_for(int64_t lo, int64_t hi, F f) {
-  par_chunks(lo, hi, [&](int, int64_t a, int64_t b) { if (a < b) f(a, b); });
-}
 // streaming (non-temporal) 16-B stores into the pinned staging: the host
 // never reads those lines again, and a plain store first reads each line for
 // ownership (a third of the packing traffic).  A pass ends with a full fence

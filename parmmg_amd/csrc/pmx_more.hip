@@ -151,7 +151,7 @@ double pmx_more_kernel_ms(pmx_ctx *ctx) {
 extern "C" int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_sols, const pmx_sol_view *new_sols,
                                int64_t npts_cap) {
   if (!ctx) return 0;
-  if (!ctx->ran || !ctx->have_pts || !ctx->have_bg || ctx->out_n != ctx->nq) {
+  if (!ctx->stepped() || !ctx->have_bg) {
     ctx->err = "pmx_interp_more: no step has run on the current uploads";
     return 0;
   }
@@ -176,7 +176,7 @@ extern "C" int pmx_interp_more(pmx_ctx *ctx, int nsol, const pmx_sol_view *old_s
   const pmx_call C{ctx, "pmx_interp_more", ctx->stream};
   ctx->more_ev_used = 0;
   // the orphans' rows first, as every consumer of the step's results
-  if (!ctx->fix_orphans()) return 0;
+  if (!ctx->ntets.fix_orphans()) return 0;
   const int64_t n = ctx->nq, np = ctx->np;
   if (n == 0) {
     CK(hipStreamSynchronize(ctx->stream));

@@ -475,14 +475,14 @@ int pmx_qualhisto(pmx_ctx *ctx, int opt, pmx_qual_stats *st) {
 static int new_mesh_qual_core(const pmx_call &C, int opt, int metRidTyp, double *qual, int64_t qstride,
                               void *dev_result, const double *sol, int S, int msize, int moff) {
   pmx_ctx *ctx = C.ctx;
-  const int64_t ne = ctx->n_ntet;
+  const int64_t ne = ctx->ntets.n;
   const int64_t n = ctx->nq;
   if (!pmx_dgrow(ctx, ctx->d_nqual, (size_t)(ne + 1))) return 0;
   StatArgs A{};
   A.xyz = ctx->d_qxyz.p;                  // the new points, dense x y z
   A.xstride = 3;
   A.vbase = 1;
-  A.tetv = ctx->d_ntetv.p;
+  A.tetv = ctx->ntets.d_v.p;
   A.ne = ne;
   A.sol = sol;
   A.S = S;
@@ -511,18 +511,18 @@ int pmx_new_mesh_qual(pmx_ctx *ctx, const int *tetra_v, int64_t tetra_stride, in
   if (!ctx) return 0;
   const pmx_call C{ctx, "pmx_new_mesh_qual", ctx->stream};
   hipSetDevice(ctx->device);
-  if (!ctx->ran || !ctx->have_pts || ctx->out_n != ctx->nq) return C.fail("run a step on the new points first");
+  if (!ctx->stepped()) return C.fail("run a step on the new points first");
   // the new tets: given here (uploaded, as pmx_upload_new_tets), or NULL for
   // the ones already uploaded; vertex j+1 = new point j
   if (tetra_v) {
     if (!pmx_upload_new_tets(ctx, tetra_v, tetra_stride, ne)) return 0;
-  } else if (!ctx->have_ntet) {
+  } else if (!ctx->ntets.have) {
     return C.fail("no new tets uploaded");
-  } else if (!ctx->ensure_tets(C.s)) {
+  } else if (!ctx->ntets.ensure_tets(C.s)) {
     return 0;
   }
-  if (qual && qual_cap < ctx->n_ntet + 1)
-    return C.fail("qual holds " + std::to_string(qual_cap) + " doubles, ne+1 = " + std::to_string(ctx->n_ntet + 1) +
+  if (qual && qual_cap < ctx->ntets.n + 1)
+    return C.fail("qual holds " + std::to_string(qual_cap) + " doubles, ne+1 = " + std::to_string(ctx->ntets.n + 1) +
                   " needed");
   // the interpolated metric, in the step's output rows (a constant-size
   // metric of the step is there too)
@@ -543,12 +543,12 @@ int pmx_new_mesh_qual_synced(pmx_ctx *ctx, const pmx_sol_view *met, int opt, int
   hipSetDevice(ctx->device);
   const int64_t qs = qual_stride ? qual_stride : (int64_t)sizeof(double);
   if (qs < (int64_t)sizeof(double)) return C.fail("bad quality stride");
-  if (!ctx->ran || !ctx->have_pts || ctx->out_n != ctx->nq) return C.fail("run a step on the new points first");
-  if (!ctx->have_ntet) return C.fail("the step's points view had no new tets");
-  if (qual && qual_cap < ctx->n_ntet + 1)
-    return C.fail("qual holds " + std::to_string(qual_cap) + " records, ne+1 = " + std::to_string(ctx->n_ntet + 1) +
+  if (!ctx->stepped()) return C.fail("run a step on the new points first");
+  if (!ctx->ntets.have) return C.fail("the step's points view had no new tets");
+  if (qual && qual_cap < ctx->ntets.n + 1)
+    return C.fail("qual holds " + std::to_string(qual_cap) + " records, ne+1 = " + std::to_string(ctx->ntets.n + 1) +
                   " needed");
-  if (!ctx->ensure_tets(C.s) || !ctx->fix_orphans()) return 0;
+  if (!ctx->ntets.ensure_tets(C.s) || !ctx->ntets.fix_orphans()) return 0;
   const int64_t n = ctx->nq, first = ctx->pts_first;
   hipStream_t s = C.s;
   if (!met || !met->m) return new_mesh_qual_core(C, opt, metRidTyp, qual, qs, dev_result, nullptr, 0, 0, 0);

@@ -178,8 +178,8 @@ static bool seq_visit_order(const pmx_call &C, const SeqBufs &b) {
   if (!C.hip(hipMemsetAsync(b.key, 0xff, (size_t)n * sizeof(unsigned), C.s), "memset") ||
       !C.hip(hipMemsetAsync(b.ctl, 0, sizeof(SeqCtl), C.s), "memset"))
     return false;
-  hipLaunchKernelGGL(k_seq_keys, dim3(seq_blocks(c->n_ntet)), dim3(256), 0, C.s, (const int4 *)c->d_ntetv.p,
-                     c->n_ntet, b.key);
+  hipLaunchKernelGGL(k_seq_keys, dim3(seq_blocks(c->ntets.n)), dim3(256), 0, C.s, (const int4 *)c->ntets.d_v.p,
+                     c->ntets.n, b.key);
   hipLaunchKernelGGL(k_seq_iota, dim3(nbp), dim3(256), 0, C.s, b.idx, b.sstart, b.sbase, n);
   if (!C.sort_pairs(c->d_sqtmp, (const unsigned *)b.key, b.key2, (const int *)b.idx, b.idx2, n, 32, "sort"))
     return false;
@@ -332,10 +332,10 @@ bool pmx_ctx::seq_replay(const VolArgs &a, hipStream_t s, bool surf, bool vol) {
   const pmx_call C{this, "sequential replay", s};
   seq_stats[0] = seq_stats[1] = seq_stats[2] = seq_stats[3] = 0;
   if (!surf && !vol) return true;
-  if (!have_ntet)
+  if (!ntets.have)
     return C.fail("PMX_RUN_SEQUENTIAL_*: the first-visit order needs the new tets (points view or pmx_upload_new_tets)");
   if (nq < 1) return true;
-  if (!ensure_tets(s)) return false;
+  if (!ntets.ensure_tets(s)) return false;
   const size_t n = (size_t)nq;
   if (!C.grow(d_sqkey, 2 * n) || !C.grow(d_sqidx, 2 * n) || !C.grow(d_sqval, 2 * n) ||
       !C.grow(d_sqint, 4 * n + SEQ_CTL_WORDS) || !C.grow(d_sqw, n) ||
