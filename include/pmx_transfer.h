@@ -24,6 +24,9 @@
  *       (src/moveinterfaces_pmmg.c:377-611) -> pmx_fix_contiguity
  *   PMMG_split_eachGrp (src/grpsplit_pmmg.c:1267-1445)
  *                                          -> pmx_split_groups / pmx_split_fetch
+ *   PMMG_update_oldGrps (src/libparmmg1.c:653) of a split's new group, with
+ *   MMG5_chkBdryTria + MMG3D_hashTria (src/grpsplit_pmmg.c:400-414)
+ *                                          -> pmx_split_adopt
  *   PMMG_merge_grps (src/mergemesh_pmmg.c:967-1073)
  *                                          -> pmx_merge_groups / pmx_merge_fetch /
  *                                             pmx_merge_adopt
@@ -347,7 +350,10 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * and after a release).
  * which = 19 / 20: the last pmx_moveifc_begin / the last pmx_moveifc_layer
  * (first to last device operation of the call; -1 before the first call, after
- * a refusal, after a release and once a background install dropped the state). */
+ * a refusal, after a release and once a background install dropped the state).
+ * which = 21: the last pmx_split_adopt into ctx (first to last device
+ * operation on ctx's stream; -1 before the first call and after a refused or
+ * failed one). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -746,6 +752,45 @@ typedef struct {
 int pmx_split_fetch(pmx_ctx *ctx, int32_t g, const pmx_split_out *out);
 /* Frees the plan's device memory (pmx_destroy does too). */
 int pmx_split_release(pmx_ctx *ctx);
+
+/* Group g of src's split plan becomes dst's uploaded group without crossing
+ * PCIe: the new group of the last split of an iteration (PMMG_split_n2mGrps
+ * with the Mmg target, src/loadbalancing_pmmg.c:135) as the next iteration's
+ * background (PMMG_update_oldGrps, src/libparmmg1.c:653).  dst ends in the
+ * state pmx_upload_background leaves, given the arrays pmx_split_fetch(src, g)
+ * returns with every solution src carries, adja = NULL, the same imet, and
+ *   surface = 1: nt, tria_v and adjt as MMG5_chkBdryTria + MMG3D_hashTria make
+ *                them of the group (src/grpsplit_pmmg.c:400-414; what
+ *                pmx_build_bdry returns for the fetched tets and adjacency:
+ *                trias in (tet, face) order, vertices in MMG5_idir order, an
+ *                edge adjacent only when exactly two trias share it), and hausd;
+ *   surface = 0: nt = 0, as pmx_merge_adopt leaves it.
+ * The library holds no tet ref: a face between tets of different ref is not a
+ * tria (as for pmx_build_bdry).  dst carries no point tags (they change at a
+ * split), and its own plans and derived data are dropped as by any upload.
+ * src's plan and background are untouched: every group can be adopted in turn
+ * into different contexts, and pmx_split_fetch still returns the same bytes.
+ * dst's stream waits for src's; the call returns when dst's copies are done,
+ * so src may release its plan right after.
+ * Returns 0, pmx_last_error(dst) naming the cause and dst unchanged but for
+ * its timing slot 21, which every call resets to -1 before its checks: a NULL
+ * context (dst NULL: pmx_last_error(NULL)); dst == src; contexts on different
+ * devices; no plan on src; g outside 0..ngrp-1; imet outside -1..nsol-1;
+ * surface not 0 or 1; hausd not finite or negative.  Non-manifold tet faces
+ * also return 0; dst then holds no background, as after a failed upload.
+ * pmx_kernel_ms(dst, 21): the adopt's device time. */
+int pmx_split_adopt(pmx_ctx *src, int32_t g, pmx_ctx *dst, int imet, int surface, double hausd);
+
+/* The installed background's boundary trias as the device holds them, whether
+ * uploaded, promoted or adopted -- a surface point's downloaded elem is a tria
+ * index in this numbering.  Returns nt.  tria: 3*(nt+1) ints in Mmg layout,
+ * rows 1..nt written (maxnt: the rows the array holds).  adjt (may be NULL):
+ * 3*nt+4 ints, all written, adjt[3*(k-1)+1+e] = 3*k'+e' -- the device keeps
+ * k' only; e' is the edge of k' that joins the same two vertices.  tria NULL:
+ * the size query -- nt is returned, nothing is copied, maxnt and adjt are not
+ * read (an adopt builds its trias on the device: ask before allocating).
+ * Returns -1, the arrays untouched: no background installed, nt > maxnt. */
+int64_t pmx_download_surface(pmx_ctx *ctx, int *tria, int64_t maxnt, int *adjt);
 
 /* A rank's groups merged into one: PMMG_merge_grps (src/mergemesh_pmmg.c:
  * 967-1073) for packed groups, the first step of PMMG_split_n2mGrps

@@ -272,6 +272,8 @@ SIGNATURES = {
                                    C.POINTER(i64), C.POINTER(i64)]),
     "pmx_split_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(SplitOut)]),
     "pmx_split_release": (C.c_int, [C.c_void_p]),
+    "pmx_split_adopt": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_int, C.c_double]),
+    "pmx_download_surface": (C.c_int64, [C.c_void_p, iptr, i64, iptr]),
     "pmx_merge_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MergeGroup), C.c_int, C.POINTER(MergeComm),
                                    C.POINTER(MergeSizes)]),
     "pmx_merge_fetch": (C.c_int, [C.c_void_p, C.POINTER(MergeOut)]),

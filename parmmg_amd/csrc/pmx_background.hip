@@ -2,10 +2,12 @@
 //
 // Three entry points install a background: pmx_upload_background (from the
 // host's Mmg arrays), pmx_promote_background (the last step's points and
-// results, already on the device) and pmx_ctx_adopt_group (a merged group on
-// the device).  Each is begin_background, grow_background, its own transfers,
-// build_records, finish_background.  build_records is the one place where
-// connectivity becomes tet records, and the only code that touches d_adja.
+// results, already on the device) and pmx_ctx_adopt_group (a merged group, or
+// one group of another context's split plan, on the device).  Each is
+// begin_background, grow_background, its own transfers, build_records,
+// finish_background.  build_records is the one place where connectivity
+// becomes tet records, and the only code that touches d_adja.
+// pmx_download_surface reads the installed trias back.
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cmath>
@@ -130,10 +132,17 @@ void begin_background(pmx_ctx *ctx, bool layout_env) {
   ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = ctx->bg_btv = false;
   ctx->stat_np = -1;
   ctx->eager_nch = 0;
+  ctx->h_nbad.p[PMX_H_BAD_TRIAS] = 0;     // only an adopt with a surface counts any
   if (layout_env) {
     ctx->compact_recs = env_compact_records();
     ctx->sample_mode = env_sample_mode();
   }
+}
+
+// the tria-sized part of the chain below, on its own for the installer that
+// learns nt on the device (an adopt with a surface calls it a second time)
+bool grow_trias(pmx_ctx *ctx, int64_t nt) {
+  return pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) && pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1));
 }
 
 // the background's device arrays for np vertices, ne tets, nt trias and rows
@@ -144,8 +153,8 @@ bool grow_background(pmx_ctx *ctx, int64_t np, int64_t ne, int64_t nt, int S, bo
   return pmx_dgrow(ctx, ctx->d_xyz, (size_t)(np + 1) * 3) && pmx_dgrow(ctx, ctx->d_tets, (size_t)(ne + 1)) &&
          (!ctx->compact_recs || pmx_dgrow(ctx, ctx->d_wrec, (size_t)(ne + 1))) &&
          pmx_dgrow(ctx, ctx->d_wfar, PMX_D_WORDS) && pmx_dgrow(ctx, ctx->d_tets_s, (size_t)std::max<int64_t>(ns, 1)) &&
-         pmx_dgrow(ctx, ctx->d_sol, (size_t)(np + 1) * std::max(S, 1)) && pmx_dgrow(ctx, ctx->d_tris, (size_t)(nt + 1)) &&
-         pmx_dgrow(ctx, ctx->d_trn, (size_t)(nt + 1)) && pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) &&
+         pmx_dgrow(ctx, ctx->d_sol, (size_t)(np + 1) * std::max(S, 1)) && grow_trias(ctx, nt) &&
+         pmx_dgrow(ctx, ctx->d_xyzq, (size_t)(np + 1)) &&
          (!btv || (pmx_dgrow(ctx, ctx->d_btv, (size_t)(ne + 1)) && pmx_dgrow(ctx, ctx->d_adja, (size_t)(4 * ne + 5))));
 }
 
@@ -179,6 +188,7 @@ bool finish_background(const pmx_call &C, const BgTail &t, Trace &tr) {
   PMX_CK(C, hipStreamSynchronize(C.s));   // the caller's host staging dies after this
   tr.mark("sync");
   if (ctx->h_nbad.p[PMX_H_NONMANIFOLD]) return C.fail("non-manifold tet faces");
+  if (ctx->h_nbad.p[PMX_H_BAD_TRIAS]) return C.fail("tria vertex or adjacency index out of range");
   ctx->fan_rot = ctx->nt > 0 && ctx->h_nbad.p[PMX_H_BAD_FANS] == 0;
   ctx->nsamp = ctx->samples_owner ? (int64_t)ctx->h_nbad.p[PMX_H_NSAMP] : 0;
   ctx->bg_btv = t.btv;
@@ -555,25 +565,120 @@ int pmx_promote_background(pmx_ctx *ctx, const pmx_mesh_view *m, int nsol, const
 
 }  // extern "C"
 
-// A device-resident group as the background (pmx_merge_adopt):
-// pmx_upload_background's device-adjacency path with nt = 0, its host packing
-// and DMA replaced by device-to-device copies
-bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
-                         const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]) {
+namespace {
+struct Axis {
+  const double *xyz;
+  int a;
+  __device__ double operator()(const int &i) const { return xyz[3 * ((int64_t)i + 1) + a]; }
+};
+}  // namespace
+
+bool pmx_bbox_device(const pmx_call &C, const double *xyz, int64_t np, DevBuf<double> &bb, DevBuf<char> &tmp,
+                     double lo[3], double hi[3]) {
+  if (!C.grow(bb, 6)) return false;
+  hipcub::CountingInputIterator<int> it(0);
+  for (int a = 0; a < 3; a++) {
+    hipcub::TransformInputIterator<double, Axis, hipcub::CountingInputIterator<int>> in(it, Axis{xyz, a});
+    size_t b = 0;
+    hipcub::DeviceReduce::Min(nullptr, b, in, bb.p + a, (int)np, C.s);
+    if (!C.grow(tmp, b) || !C.ok(hipcub::DeviceReduce::Min(tmp.p, b, in, bb.p + a, (int)np, C.s), "bbox"))
+      return false;
+    hipcub::DeviceReduce::Max(nullptr, b, in, bb.p + 3 + a, (int)np, C.s);
+    if (!C.grow(tmp, b) || !C.ok(hipcub::DeviceReduce::Max(tmp.p, b, in, bb.p + 3 + a, (int)np, C.s), "bbox"))
+      return false;
+  }
+  double h[6];
+  if (!C.read_words(h, (const double *)bb.p, 6, "bbox")) return false;
+  for (int a = 0; a < 3; a++) { lo[a] = h[a]; hi[a] = h[3 + a]; }
+  return true;
+}
+
+// A device-resident group as the background (pmx_merge_adopt, pmx_split_adopt):
+// pmx_upload_background's device-adjacency path, its host packing and DMA
+// replaced by device-to-device copies or a row gather, its host trias by none
+// (nt = 0) or by the boundary build on the records' neighbour fields
+bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const AdoptSrc &src, const SolDesc &sd, int64_t np,
+                         int64_t ne) {
   const pmx_call C{ctx, who, ctx->stream};
   begin_background(ctx, true);
   if (np < 1 || ne < 1 || np >= (1LL << 31) - 1 || 4 * ne >= (1LL << 31)) return C.fail("mesh sizes out of range");
   if (!grow_background(ctx, np, ne, 0, sd.S, true)) return false;
   hipStream_t st = ctx->stream;
   const size_t hs_n = (size_t)(np + 1) * std::max(sd.S, 1);
-  if (!C.hip(hipMemcpyAsync(ctx->d_xyz.p, xyz, (size_t)(np + 1) * 24, hipMemcpyDeviceToDevice, st), "points") ||
-      !C.hip(hipMemcpyAsync(ctx->d_btv.p, tv, (size_t)(ne + 1) * sizeof(int4), hipMemcpyDeviceToDevice, st), "tets") ||
-      !C.hip(sd.S > 0 ? hipMemcpyAsync(ctx->d_sol.p, sol, hs_n * sizeof(double), hipMemcpyDeviceToDevice, st)
-                      : hipMemsetAsync(ctx->d_sol.p, 0, hs_n * sizeof(double), st), "solutions") ||
+  if (src.idx) {
+    launch_gather_rows(src.idx, np, src.xyz, src.sol, sd.S, ctx->d_xyz.p, ctx->d_sol.p, st);
+    if (sd.S == 0 && !C.hip(hipMemsetAsync(ctx->d_sol.p, 0, hs_n * sizeof(double), st), "solutions")) return false;
+  } else if (!C.hip(hipMemcpyAsync(ctx->d_xyz.p, src.xyz, (size_t)(np + 1) * 24, hipMemcpyDeviceToDevice, st), "points") ||
+             !C.hip(sd.S > 0 ? hipMemcpyAsync(ctx->d_sol.p, src.sol, hs_n * sizeof(double), hipMemcpyDeviceToDevice, st)
+                             : hipMemsetAsync(ctx->d_sol.p, 0, hs_n * sizeof(double), st), "solutions")) {
+    return false;
+  }
+  if (!C.hip(hipMemsetAsync(ctx->d_btv.p, 0, sizeof(int4), st), "tets") ||
+      !C.hip(hipMemcpyAsync(ctx->d_btv.p + 1, src.tv, (size_t)ne * sizeof(int4), hipMemcpyDeviceToDevice, st), "tets") ||
       !C.hip(hipMemsetAsync(ctx->d_tris.p, 0, sizeof(TriRec), st), "trias"))
     return false;
   if (!ctx->build_records(ctx->d_btv.p, nullptr, ne, np, ctx->records_current(), st)) return false;
   ctx->sd = sd;
   Trace tr("adopt");
-  return finish_background(C, {np, ne, 0, 0.0, lo, hi, nullptr, true, true, nullptr}, tr);
+  double lo[3], hi[3];
+  if (!pmx_bbox_device(C, ctx->d_xyz.p, np, ctx->d_bb, ctx->d_bbtmp, lo, hi)) return false;
+  tr.mark("copies + records + bbox");
+  int64_t nt = 0;
+  if (src.surface) {
+    // the bbox's sync has brought the face matching's count: stop before a
+    // surface is built on an adjacency that left shared faces at 0
+    if (ctx->h_nbad.p[PMX_H_NONMANIFOLD]) return C.fail("non-manifold tet faces");
+    // adja == 0 <=> the record's neighbour field is 0: d_adja itself stays build_records' alone
+    if (!pmx_bdry_device(C, ctx->d_btv.p, reinterpret_cast<const int *>(ctx->d_tets.p), 8, 4, ne, np, true, 4 * ne,
+                         ctx->bdry, &nt, nullptr, nullptr))
+      return false;
+    if (!grow_trias(ctx, nt)) return false;
+    if (nt > 0) {
+      unsigned *bad = ctx->d_wfar.p + PMX_D_BAD_TRIAS;
+      if (!C.hip(hipMemsetAsync(bad, 0, sizeof(unsigned), st), "trias")) return false;
+      launch_tri_records(ctx->bdry.tria.p, ctx->bdry.adjt.p, nt, np, ctx->d_tris.p, bad, st);
+      if (!C.hip(hipMemcpyAsync(ctx->h_nbad.p + PMX_H_BAD_TRIAS, bad, sizeof(unsigned), hipMemcpyDeviceToHost, st), "trias"))
+        return false;
+    } else if (!C.hip(hipMemsetAsync(ctx->d_tris.p, 0, sizeof(TriRec), st), "trias")) {
+      return false;
+    }
+    tr.mark("surface");
+  }
+  return finish_background(C, {np, ne, nt, src.surface ? src.hausd : 0.0, lo, hi, nullptr, true, true, nullptr}, tr);
+}
+
+extern "C" int64_t pmx_download_surface(pmx_ctx *ctx, int *tria, int64_t maxnt, int *adjt) {
+  if (!ctx) return -1;
+  const pmx_call C{ctx, "pmx_download_surface", ctx->stream};
+  if (!ctx->have_bg) return C.fail("no background installed"), -1;
+  const int64_t nt = ctx->nt;
+  if (!tria) return nt;                          // the size query: nothing is copied
+  if (nt > maxnt) return C.fail("more trias than maxnt"), -1;
+  hipSetDevice(ctx->device);
+  std::vector<TriRec> h((size_t)(nt + 1));
+  if (!C.hip(hipMemcpyAsync(h.data(), ctx->d_tris.p, h.size() * sizeof(TriRec), hipMemcpyDeviceToHost, C.s), "download") ||
+      !C.sync("download"))
+    return -1;
+  for (int64_t k = 1; k <= nt; k++)
+    for (int l = 0; l < 3; l++) tria[3 * k + l] = h[(size_t)k].v[l];
+  if (!adjt) return nt;
+  // the records keep the neighbouring tria only: its edge is the one that
+  // joins the same two vertices
+  adjt[0] = adjt[3 * nt + 1] = adjt[3 * nt + 2] = adjt[3 * nt + 3] = 0;
+  for (int64_t k = 1; k <= nt; k++) {
+    const TriRec &t = h[(size_t)k];
+    for (int e = 0; e < 3; e++) {
+      const int nb = t.nb[e], a = t.v[(e + 1) % 3], b = t.v[(e + 2) % 3];
+      int en = 0;
+      if (nb > 0 && nb <= nt) {
+        const TriRec &o = h[(size_t)nb];
+        for (int f = 0; f < 3; f++) {
+          const int c = o.v[(f + 1) % 3], d = o.v[(f + 2) % 3];
+          if ((c == a && d == b) || (c == b && d == a)) en = f;
+        }
+      }
+      adjt[3 * (k - 1) + 1 + e] = nb > 0 ? 3 * nb + en : 0;
+    }
+  }
+  return nt;
 }

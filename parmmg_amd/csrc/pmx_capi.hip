@@ -553,7 +553,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && which == 7) return pmx_more_kernel_ms(ctx);
   if (ctx && which >= 8 && which <= 11) return pmx_graph_kernel_ms(ctx, which);
   if (ctx && (which == 12 || which == 13)) return pmx_contig_kernel_ms(ctx, which);
-  if (ctx && (which == 14 || which == 15)) return pmx_split_kernel_ms(ctx, which);
+  if (ctx && (which == 14 || which == 15 || which == 21)) return pmx_split_kernel_ms(ctx, which);
   if (ctx && which >= 16 && which <= 18) return pmx_merge_kernel_ms(ctx, which);
   if (ctx && (which == 19 || which == 20)) return pmx_moveifc_kernel_ms(ctx, which);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;

@@ -32,6 +32,7 @@ enum {
   PMX_H_FAR_NEXT = 3,           // ... of d_wrec_next
   PMX_H_BAD_FANS = 4,           // check_fans: vertices whose fan the rotation cannot build
   PMX_H_NSAMP = 5,              // entries of the vertex-owner hint sample
+  PMX_H_BAD_TRIAS = 6,          // device-built trias outside stage_trias' ranges (0 for the host's trias)
   PMX_H_WORDS = 8
 };
 enum {
@@ -40,7 +41,20 @@ enum {
   PMX_D_FANS_STEP = 2,          // bad fans of the step's rotation
   PMX_D_FANS_CHECK = 3,         // ... of the upload's check
   PMX_D_NSAMP = 4,              // owner-sample count
+  PMX_D_BAD_TRIAS = 5,          // k_tri_records' range check
   PMX_D_WORDS = 8
+};
+
+// The device buffers of one boundary build (pmx_bdry_device, pmx_topo.hip):
+// the trias (3 (nt + 1) ints, Mmg layout, row 0 zero) and their adjt
+// (3 nt + 4 ints), then the scratch -- boundary faces per tet and their scan,
+// edge buckets, edge records, the bucket of every record, one scan scratch
+// per scan (no free while the first is queued)
+struct BdryDev {
+  DevBuf<int> tria, adjt, bof;
+  DevBuf<unsigned> tcnt, tpos, cnt, off;
+  DevBuf<int2> rec;
+  DevBuf<char> tmp, tmp2;
 };
 
 // Where build_records puts a background's tet records: the buffers, the
@@ -301,6 +315,16 @@ struct pmx_ctx {
   struct pmx_split_plan *split = nullptr;
   bool split_valid = false;
   double split_plan_ms = -1.0, split_fetch_ms = -1.0;
+  // A device-resident group as this context's background (pmx_ctx_adopt_group;
+  // pmx_split_adopt on the receiving context): the bounding-box reduction's
+  // result and scratch, the boundary build's buffers, the event that orders
+  // this stream behind the giving context's, the event pair and the device
+  // time of the last pmx_split_adopt into this context
+  DevBuf<double> d_bb;
+  DevBuf<char> d_bbtmp;
+  BdryDev bdry;
+  DevEvent ev_give, adopt_ev[2];
+  double split_adopt_ms = -1.0;
   // Group merge (pmx_merge_groups / _fetch / _maps / _adopt, pmx_merge.hip):
   // the plan with its device buffers, independent of the background (an
   // upload or a promotion leaves it alone); device times of the last plan /
@@ -493,8 +517,8 @@ template <class R> inline bool read_pub(const pmx_call &C, R &r) {
 // pmx_kernel_ms(ctx, 12 / 13): the labelling / the replay and recolour kernels
 // of the last pmx_contiguity or pmx_fix_contiguity, summed (pmx_contig.hip)
 double pmx_contig_kernel_ms(pmx_ctx *ctx, int which);
-// pmx_kernel_ms(ctx, 14 / 15): the last split plan / the last fetch; the plan
-// and its buffers freed (pmx_split.hip)
+// pmx_kernel_ms(ctx, 14 / 15 / 21): the last split plan / the last fetch / the
+// last pmx_split_adopt into ctx; the plan and its buffers freed (pmx_split.hip)
 double pmx_split_kernel_ms(pmx_ctx *ctx, int which);
 void pmx_split_free(pmx_ctx *ctx);
 // pmx_kernel_ms(ctx, 16 / 17 / 18): the last merge plan / fetch / adopt; the
@@ -508,12 +532,35 @@ bool pmx_merge_tet_group(pmx_ctx *ctx, const int **tgrp, int64_t *ne);
 // and its buffers freed (pmx_moveifc.hip)
 double pmx_moveifc_kernel_ms(pmx_ctx *ctx, int which);
 void pmx_moveifc_free(pmx_ctx *ctx);
-// A group that is already on the device (connectivity tv: 1-based int4, slot 0
-// unused; xyz: 3 (np + 1) doubles; sol: (np + 1) max(S, 1) doubles, interleaved;
-// bounding box lo / hi) becomes the uploaded group, as pmx_upload_background
-// with adja = NULL and nt = 0 leaves it; the copies are device to device on
-// the context stream (pmx_background.hip).  false + ctx->err, no background kept.
-bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const int4 *tv, const double *xyz, const double *sol,
-                         const SolDesc &sd, int64_t np, int64_t ne, const double lo[3], const double hi[3]);
+// Boundary trias and their edge adjacency of device connectivity tv (1-based
+// int4, slot 0 unused) into B, on C's stream (pmx_topo.hip): a face of a valid
+// tet is a tria when its adjacency entry adj[adj_stride * k + adj_off + f] is 0
+// (Mmg's adja: stride 4, off -3; the tet records' neighbour fields: 8, 4), in
+// (tet, face) order, vertices in MMG5_idir order; with want_adjt an edge has a
+// neighbour when exactly two trias share it.  *nt: their number (the stream
+// is synchronised once to read it; more than maxnt fails before anything
+// tria-sized is allocated).  e0 / e1 (may be null): recorded before the first
+// and after the last kernel.
+bool pmx_bdry_device(const pmx_call &C, const int4 *tv, const int *adj, int adj_stride, int adj_off, int64_t ne,
+                     int64_t np, bool want_adjt, int64_t maxnt, BdryDev &B, int64_t *nt, hipEvent_t e0,
+                     hipEvent_t e1);
+// the bounding box of the rows 1..np of xyz (device, 24-B rows) on C's stream,
+// which is synchronised; bb: 6 doubles, tmp: hipcub's scratch (pmx_background.hip)
+bool pmx_bbox_device(const pmx_call &C, const double *xyz, int64_t np, DevBuf<double> &bb, DevBuf<char> &tmp,
+                     double lo[3], double hi[3]);
+// A group that is already on the device becomes the uploaded group, as
+// pmx_upload_background with adja = NULL leaves it; the copies are device to
+// device on the context stream (pmx_background.hip).  false + ctx->err, no
+// background kept.
+struct AdoptSrc {
+  const int4 *tv;            // the tets 1..ne (tv[0] is tet 1)
+  const double *xyz, *sol;   // source rows: row r at xyz + 3 r and sol + S r (interleaved solutions)
+  const int *idx;            // nullptr: the group's row i is source row i, row 0 included;
+                             // else its row i is source row idx[i - 1] (np entries) and row 0 is zeroed
+  bool surface;              // false: nt = 0; true: the boundary trias and their adjacency are built
+  double hausd;              // ... and this is the background's hausd
+};
+bool pmx_ctx_adopt_group(pmx_ctx *ctx, const char *who, const AdoptSrc &src, const SolDesc &sd, int64_t np,
+                         int64_t ne);
 // error of a call made without a context (pmx_last_error(NULL), per thread)
 void pmx_set_noctx_error(const char *msg);

@@ -152,6 +152,15 @@ struct OrphanRows {
 };
 void launch_orphans(const uint8_t *mk, int64_t n, uint8_t keep, const OrphanRows &r, hipStream_t s);
 void launch_patch_rows(const int4 *ent, const double *vals, int64_t n, int S, double *sol, hipStream_t s);
+// a split group as the background (pmx_split_adopt): xyz[i] / sol[i] = row
+// idx[i - 1] of sxyz / ssol for i = 1..n, row 0 zeroed (S = 0: sol is not touched)
+void launch_gather_rows(const int *idx, int64_t n, const double *sxyz, const double *ssol, int S, double *xyz,
+                        double *sol, hipStream_t s);
+// Mmg-layout trias (3 (nt + 1) ints) and adjt (3 nt + 4 ints) on the device ->
+// TriRec records 0..nt, record 0 zeroed; an entry outside the range the host's
+// staging accepts (vertex 1..np, adjt >= 0, adjt / 3 <= nt) counts into *bad
+void launch_tri_records(const int *tria, const int *adjt, int64_t nt, int64_t np, TriRec *tris, unsigned *bad,
+                        hipStream_t s);
 // new points, every step (the tag dispatch of the reference's vertex loop,
 // src/interpmesh_pmmg.c:541-560): kinds (mark != NULL: the orphan marks of
 // the new tets, 0 = in no valid new tet) and the order-preserving compaction into

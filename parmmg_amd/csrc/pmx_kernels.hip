@@ -791,6 +791,62 @@ void launch_patch_rows(const int4 *ent, const double *vals, int64_t n, int S, do
   const int64_t nb = std::min<int64_t>((n + 255) / 256, 4096);
   hipLaunchKernelGGL(k_patch_rows, dim3((unsigned)nb), dim3(256), 0, s, ent, vals, n, S, sol);
 }
+// One thread per 8-byte word of the destination, xyz's 3 (n + 1) words first,
+// then sol's S (n + 1): word t is stored at t, so a wave stores 512 contiguous
+// bytes, and the words of one source row are read by adjacent lanes.  idx is
+// a first-visit numbering: mostly ascending, so neighbouring rows share lines.
+__global__ __launch_bounds__(256) void k_gather_rows(const int *__restrict__ idx, int64_t n,
+                                                     const double *__restrict__ sxyz,
+                                                     const double *__restrict__ ssol, int S,
+                                                     double *__restrict__ xyz, double *__restrict__ sol) {
+  const int64_t nx = 3 * (n + 1), nw = nx + (int64_t)S * (n + 1);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nw; t += (int64_t)gridDim.x * blockDim.x) {
+    if (t < nx) {
+      const int64_t i = t / 3;
+      const int c = (int)(t - 3 * i);
+      xyz[t] = i ? sxyz[3 * (int64_t)idx[i - 1] + c] : 0.0;
+    } else {
+      const int64_t u = t - nx, i = u / S;
+      const int c = (int)(u - S * i);
+      sol[u] = i ? ssol[(int64_t)S * idx[i - 1] + c] : 0.0;
+    }
+  }
+}
+void launch_gather_rows(const int *idx, int64_t n, const double *sxyz, const double *ssol, int S, double *xyz,
+                        double *sol, hipStream_t s) {
+  const int64_t nw = (int64_t)(3 + S) * (n + 1);
+  const int64_t nb = std::min<int64_t>(std::max<int64_t>((nw + 255) / 256, 1), 1 << 20);
+  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)nb), dim3(256), 0, s, idx, n, sxyz, ssol, S, xyz, sol);
+}
+
+// One thread per tria: its 3 vertices and 3 adjt entries in, one 32-B record
+// out (two 16-B stores, consecutive lanes consecutive records).  The ranges
+// are stage_trias' (pmx_background.hip).
+__global__ __launch_bounds__(256) void k_tri_records(const int *__restrict__ tria, const int *__restrict__ adjt,
+                                                     int64_t nt, int64_t np, TriRec *__restrict__ tris,
+                                                     unsigned *__restrict__ bad) {
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt;
+       k += (int64_t)gridDim.x * blockDim.x) {
+    int4 v = make_int4(0, 0, 0, 0), nb = make_int4(0, 0, 0, 0);
+    if (k) {
+      const int a0 = adjt[3 * (k - 1) + 1], a1 = adjt[3 * (k - 1) + 2], a2 = adjt[3 * (k - 1) + 3];
+      v = make_int4(tria[3 * k], tria[3 * k + 1], tria[3 * k + 2], 0);
+      nb = make_int4(a0 / 3, a1 / 3, a2 / 3, 0);
+      if (v.x < 1 || v.x > np || v.y < 1 || v.y > np || v.z < 1 || v.z > np || a0 < 0 || a1 < 0 || a2 < 0 ||
+          nb.x > nt || nb.y > nt || nb.z > nt)
+        atomicAdd(bad, 1u);
+    }
+    int4 *r = reinterpret_cast<int4 *>(tris + k);
+    r[0] = v;
+    r[1] = nb;
+  }
+}
+void launch_tri_records(const int *tria, const int *adjt, int64_t nt, int64_t np, TriRec *tris, unsigned *bad,
+                        hipStream_t s) {
+  const int64_t nb = std::min<int64_t>(std::max<int64_t>((nt + 256) / 256, 1), 1 << 20);
+  hipLaunchKernelGGL(k_tri_records, dim3((unsigned)nb), dim3(256), 0, s, tria, adjt, nt, np, tris, bad);
+}
+
 void launch_build_tetrec(const int4 *tv, const int *adja, int64_t ne, int stride, TetRec *tets, int4 *sample,
                          hipStream_t s) {
   const int64_t nb = std::min<int64_t>(std::max<int64_t>((ne + 256) / 256, 1), 16384);

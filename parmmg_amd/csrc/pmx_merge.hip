@@ -277,13 +277,6 @@ __global__ __launch_bounds__(256) void k_mg_deinterleave(const double *__restric
   gs[np * sd.off[is] + i * sd.size[is] + (c - sd.off[is])] = msol[(int64_t)sd.S * (i + 1) + c];
 }
 
-// coordinate a of point i + 1
-struct Axis {
-  const double *xyz;
-  int a;
-  __device__ double operator()(const int &i) const { return xyz[3 * ((int64_t)i + 1) + a]; }
-};
-
 }  // namespace
 
 struct pmx_merge_plan {
@@ -291,7 +284,7 @@ struct pmx_merge_plan {
   int ngrp = 0, next_node = 0;
   SolDesc sd{};
   std::vector<int> gt;                   // the group table, GT_ROWS x (ngrp + 1)
-  DevBuf<double> cxyz, csol, mxyz, msol, gs, bb;
+  DevBuf<double> cxyz, csol, mxyz, msol, gs;
   DevBuf<int4> ctet, mtet;
   DevBuf<int> gtab, nep, nes, fet, fe1, fe2, extn, extf, eoff, nseed, fseed, crank, urank, hrank, turank, pmap,
       psrc, pgrp, pold, tnew, tgrp, told, fval, em, epos, extn_new, on1, on2, of1, of2;
@@ -323,7 +316,6 @@ struct Merge : pmx_call {
   bool word(int *dst, const int *src, const char *what) { return read_words(dst, src, 1, what); }
 
   bool plan(int64_t nitemN, int64_t nitemF);
-  bool bbox(double lo[3], double hi[3]);
 };
 
 // the packed groups are on their way to the device; the rest happens there
@@ -406,26 +398,6 @@ bool Merge::plan(int64_t nitemN, int64_t nitemF) {
   if (h[MC_TWICE]) return fail("a merged point appears twice in the external node communicator of its first appearance");
   P.nnode = nnode;
   P.ne = T;
-  return true;
-}
-
-bool Merge::bbox(double lo[3], double hi[3]) {
-  pmx_merge_plan &P = *pl;
-  if (!pmx_dgrow(ctx, P.bb, 6)) return false;
-  hipcub::CountingInputIterator<int> it(0);
-  for (int a = 0; a < 3; a++) {
-    hipcub::TransformInputIterator<double, Axis, hipcub::CountingInputIterator<int>> in(it, Axis{P.mxyz.p, a});
-    size_t b = 0;
-    hipcub::DeviceReduce::Min(nullptr, b, in, P.bb.p + a, (int)P.np, s);
-    if (!pmx_dgrow(ctx, P.tmp, b) || !ok(hipcub::DeviceReduce::Min(P.tmp.p, b, in, P.bb.p + a, (int)P.np, s), "bbox"))
-      return false;
-    hipcub::DeviceReduce::Max(nullptr, b, in, P.bb.p + 3 + a, (int)P.np, s);
-    if (!pmx_dgrow(ctx, P.tmp, b) || !ok(hipcub::DeviceReduce::Max(P.tmp.p, b, in, P.bb.p + 3 + a, (int)P.np, s), "bbox"))
-      return false;
-  }
-  double h[6];
-  if (!read_words(h, (const double *)P.bb.p, 6, "bbox")) return false;
-  for (int a = 0; a < 3; a++) { lo[a] = h[a]; hi[a] = h[3 + a]; }
   return true;
 }
 
@@ -712,11 +684,11 @@ int pmx_merge_adopt(pmx_ctx *ctx, int imet) {
   if (imet < -1 || imet >= P.sd.nsol) { M.fail("imet outside -1..nsol-1"); return 0; }
   ctx->merge_adopt_ms = -1.0;
   if (!M.ok(hipEventRecord(P.ev[0], M.s), "event record")) return 0;
-  double lo[3], hi[3];
-  if (!M.bbox(lo, hi)) return 0;
   SolDesc sd = P.sd;
   sd.imet = imet;
-  if (!pmx_ctx_adopt_group(ctx, "pmx_merge_adopt", P.mtet.p, P.mxyz.p, P.msol.p, sd, P.np, P.ne, lo, hi)) return 0;
+  // rows as they are (no gather), no surface: a merged group needs none
+  const AdoptSrc src{P.mtet.p + 1, P.mxyz.p, P.msol.p, nullptr, false, 0.0};
+  if (!pmx_ctx_adopt_group(ctx, "pmx_merge_adopt", src, sd, P.np, P.ne)) return 0;
   if (!M.ok(hipEventRecord(P.ev[1], M.s), "event record") || !M.sync("adopt")) return 0;
   float ms = 0.f;
   if (!M.ok(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]), "event time")) return 0;

@@ -4,6 +4,8 @@
 //   (src/grpsplit_pmmg.c:1267-1445): PMMG_splitGrps_countTetPerGrp
 //   (:1106-1116), PMMG_splitGrps_fillGroup (:819-1094) and the communicator
 //   updates it calls (:606-795)
+// pmx_split_adopt <- PMMG_update_oldGrps (src/libparmmg1.c:653) for one new
+//   group: it becomes another context's background, on the device
 //
 // Semantics: DESIGN.md section 4, "Group split".  The reference is one
 // sequential pass with running counters; here every order and counter is a
@@ -35,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include "pmx_device.h"
 #include "pmx_internal.h"
@@ -665,7 +668,9 @@ void pmx_split_free(pmx_ctx *ctx) {
   delete P;
 }
 
-double pmx_split_kernel_ms(pmx_ctx *ctx, int which) { return which == 14 ? ctx->split_plan_ms : ctx->split_fetch_ms; }
+double pmx_split_kernel_ms(pmx_ctx *ctx, int which) {
+  return which == 14 ? ctx->split_plan_ms : which == 15 ? ctx->split_fetch_ms : ctx->split_adopt_ms;
+}
 
 extern "C" {
 
@@ -791,6 +796,50 @@ int pmx_split_fetch(pmx_ctx *ctx, int32_t g, const pmx_split_out *out) {
     out->adja[0] = 0;
     for (int i = 1; i <= 4; i++) out->adja[4 * neg + i] = 0;
   }
+  return 1;
+}
+
+// Group g of src's plan as dst's background: the rows through the plan's
+// point_old slice, the connectivity from its vcat slice, everything else as
+// any adopt (pmx_ctx_adopt_group).  dst's stream waits for src's; the call
+// returns once dst's copies are done (finish_background synchronises), so src
+// may release or replace its plan afterwards.
+int pmx_split_adopt(pmx_ctx *src, int32_t g, pmx_ctx *dst, int imet, int surface, double hausd) {
+  if (!dst) {
+    pmx_set_noctx_error("pmx_split_adopt: dst is NULL");
+    return 0;
+  }
+  const pmx_call C{dst, "pmx_split_adopt", dst->stream};
+  dst->split_adopt_ms = -1.0;
+  if (!src) return C.fail("src is NULL");
+  if (src == dst) return C.fail("dst is src: a context cannot adopt from its own plan (the install drops it)");
+  if (src->device != dst->device) return C.fail("src and dst are on different devices");
+  if (!src->split || !src->split_valid || !src->have_bg)
+    return C.fail("no plan on src: call pmx_split_groups (a background upload or promotion drops the plan)");
+  const pmx_split_plan &P = *src->split;
+  if (g < 0 || g >= P.ngrp) return C.fail("group out of range");
+  if (imet < -1 || imet >= src->sd.nsol) return C.fail("imet outside -1..nsol-1");
+  if (surface != 0 && surface != 1) return C.fail("surface must be 0 or 1");
+  if (!std::isfinite(hausd) || hausd < 0.0) return C.fail("hausd must be finite and >= 0");
+  hipSetDevice(dst->device);
+  const int64_t t0 = P.row(GT_T, g), neg = P.row(GT_T, g + 1) - t0;
+  const int64_t p0 = P.row(GT_P, g), npg = P.row(GT_P, g + 1) - p0;
+  SolDesc sd = src->sd;
+  sd.imet = imet;
+  sd.metric_const = 0;
+  if (!pmx_create_events(dst->adopt_ev) || !dst->ev_give.create(false)) return C.fail("event");
+  // everything src's stream has queued (the plan, a fetch's gather) is done
+  // before dst's stream reads src's buffers
+  PMX_CK(C, hipEventRecord(dst->ev_give, src->stream));
+  PMX_CK(C, hipStreamWaitEvent(dst->stream, dst->ev_give, 0));
+  PMX_CK(C, hipEventRecord(dst->adopt_ev[0], dst->stream));
+  const AdoptSrc from{P.vcat.p + t0, src->d_xyz.p, src->d_sol.p, P.pcat.p + p0, surface == 1, hausd};
+  if (!pmx_ctx_adopt_group(dst, "pmx_split_adopt", from, sd, npg, neg)) return 0;
+  PMX_CK(C, hipEventRecord(dst->adopt_ev[1], dst->stream));
+  if (!C.sync("adopt")) return 0;
+  float ms = 0.f;
+  PMX_CK(C, hipEventElapsedTime(&ms, dst->adopt_ev[0], dst->adopt_ev[1]));
+  dst->split_adopt_ms = ms;
   return 1;
 }
 

@@ -8,6 +8,8 @@
 //                    of the faces without a neighbour, in (tet, face) order,
 //                    vertices in MMG5_idir order, and their edge adjacency
 //                    adjt[3*(k-1)+1+e] = 3*k'+e'
+// pmx_bdry_device    its device part, on device arrays: pmx_build_bdry wraps
+//                    it, an adopt with a surface calls it on the tet records
 //
 // Hash-free face matching: every face (edge) record goes to the bucket of its
 // smallest vertex (count, exclusive scan, scatter); a face's partner is the
@@ -171,21 +173,28 @@ static void launch_face_match(const int4 *rec, int64_t ne, int64_t np, const uns
 
 // ---- boundary trias and their edge adjacency -------------------------------------
 
-__global__ __launch_bounds__(256) void k_bdry_count(const int4 *__restrict__ tv,
-                                                    const int *__restrict__ adja, int64_t ne,
+// where a tet's face adjacency is read: entry (k, f) at p[stride * k + off + f],
+// 0 = no neighbour.  Mmg's adja (4 ne + 5 ints): stride 4, off -3; the tet
+// records' neighbour fields: stride 8, off 4
+struct FaceAdj {
+  const int *p;
+  int stride, off;
+  __device__ __forceinline__ int operator()(int64_t k, int f) const { return p[stride * k + off + f]; }
+};
+
+__global__ __launch_bounds__(256) void k_bdry_count(const int4 *__restrict__ tv, FaceAdj adja, int64_t ne,
                                                     unsigned *__restrict__ cnt) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
   if (k > ne) return;
   unsigned c = 0;
   if (tv[k].x > 0) {                              // !MG_EOK tets have no faces
 #pragma unroll
-    for (int f = 0; f < 4; f++) c += adja[4 * (k - 1) + 1 + f] == 0 ? 1u : 0u;
+    for (int f = 0; f < 4; f++) c += adja(k, f) == 0 ? 1u : 0u;
   }
   cnt[k - 1] = c;
 }
 
-__global__ __launch_bounds__(256) void k_bdry_write(const int4 *__restrict__ tv,
-                                                    const int *__restrict__ adja, int64_t ne,
+__global__ __launch_bounds__(256) void k_bdry_write(const int4 *__restrict__ tv, FaceAdj adja, int64_t ne,
                                                     const unsigned *__restrict__ pos,
                                                     int *__restrict__ tria) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1;
@@ -195,7 +204,7 @@ __global__ __launch_bounds__(256) void k_bdry_write(const int4 *__restrict__ tv,
   const int v[4] = {t.x, t.y, t.z, t.w};
   int64_t p = pos[k - 1] + 1;                    // 1-based tria index, (k, f) order
   for (int f = 0; f < 4; f++) {
-    if (adja[4 * (k - 1) + 1 + f]) continue;
+    if (adja(k, f)) continue;
     tria[3 * p + 0] = v[TOPO_IDIR[f][0]];
     tria[3 * p + 1] = v[TOPO_IDIR[f][1]];
     tria[3 * p + 2] = v[TOPO_IDIR[f][2]];
@@ -349,6 +358,52 @@ bool pmx_ctx_build_adja_device(pmx_ctx *ctx, const int4 *tv, int64_t ne, int64_t
   return true;
 }
 
+// MMG5_chkBdryTria + MMG3D_hashTria on device arrays (pmx_internal.h): count,
+// scan, one control word down for nt, write, then the edges bucketed by their
+// smaller vertex and matched.  Everything stays in B.
+bool pmx_bdry_device(const pmx_call &C, const int4 *tv, const int *adj, int adj_stride, int adj_off, int64_t ne,
+                     int64_t np, bool want_adjt, int64_t maxnt, BdryDev &B, int64_t *nt_out, hipEvent_t e0,
+                     hipEvent_t e1) {
+  pmx_ctx *ctx = C.ctx;
+  hipStream_t s = C.s;
+  const FaceAdj fa{adj, adj_stride, adj_off};
+  unsigned *tcnt = local(ctx, B.tcnt, (size_t)(ne + 1));
+  unsigned *tpos = local(ctx, B.tpos, (size_t)(ne + 1));
+  if (!tcnt || !tpos) return C.fail("hipMalloc");
+  hipMemsetAsync(tcnt, 0, sizeof(unsigned) * (size_t)(ne + 1), s);
+  if (e0) hipEventRecord(e0, s);
+  hipLaunchKernelGGL(k_bdry_count, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, fa, ne, tcnt);
+  if (!C.exclusive_sum(B.tmp, (const unsigned *)tcnt, tpos, ne + 1, "scan")) return C.fail("scan");
+  unsigned nt_u = 0;
+  if (!C.read_words(&nt_u, (const unsigned *)(tpos + ne), 1, "boundary face count")) return false;
+  const int64_t nt = nt_u;
+  if (nt > maxnt) return C.fail("more boundary faces than maxnt");
+  int *dtria = local(ctx, B.tria, (size_t)(3 * (nt + 1)));
+  if (!dtria) return C.fail("hipMalloc");
+  hipMemsetAsync(dtria, 0, sizeof(int) * 3, s);
+  hipLaunchKernelGGL(k_bdry_write, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, fa, ne, tpos, dtria);
+  if (want_adjt && nt > 0) {
+    unsigned *cnt = local(ctx, B.cnt, (size_t)(np + 2));
+    unsigned *off = local(ctx, B.off, (size_t)(np + 2));
+    int2 *rec = local(ctx, B.rec, (size_t)(3 * nt));
+    int *bof = local(ctx, B.bof, (size_t)(3 * nt));
+    int *dadjt = local(ctx, B.adjt, (size_t)(3 * nt + 4));
+    if (!cnt || !off || !rec || !bof || !dadjt) return C.fail("hipMalloc");
+    hipMemsetAsync(cnt, 0, sizeof(unsigned) * (size_t)(np + 2), s);
+    hipMemsetAsync(dadjt, 0, sizeof(int) * (size_t)(3 * nt + 4), s);
+    hipLaunchKernelGGL(k_edge_count, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, dtria, nt, cnt);
+    if (!C.exclusive_sum(B.tmp2, (const unsigned *)cnt, off, np + 2, "scan")) return C.fail("scan");
+    hipMemcpyAsync(cnt, off, sizeof(unsigned) * (size_t)(np + 2), hipMemcpyDeviceToDevice, s);
+    hipLaunchKernelGGL(k_edge_scatter, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, dtria, nt, cnt, rec);
+    hipLaunchKernelGGL(k_bucket_of, dim3(pmx_call::blocks(np + 1)), dim3(256), 0, s, off, np + 1, bof);
+    hipLaunchKernelGGL(k_edge_match, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, rec, 3 * nt, off, bof,
+                       dadjt);
+  }
+  if (e1) hipEventRecord(e1, s);
+  *nt_out = nt;
+  return true;
+}
+
 extern "C" {
 
 int pmx_build_adja(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v, int64_t tetra_stride,
@@ -392,60 +447,26 @@ int64_t pmx_build_bdry(pmx_ctx *ctx, int64_t ne, int64_t np, const int *tetra_v,
   hipStream_t s = ctx->stream;
   const pmx_call C{ctx, "pmx_build_bdry", s};
   DevBuf<int4> b_tv;
-  DevBuf<int> b_adja, b_tria, b_bof, b_adjt;
-  DevBuf<unsigned> b_tcnt, b_tpos, b_cnt, b_off;
-  DevBuf<int2> b_rec;
-  DevBuf<char> tmp, tmp2;                        // one per scan: no free while the first is queued
+  DevBuf<int> b_adja;
+  BdryDev B;
   int4 *tv = upload_tets(ctx, ne, np, tetra_v, tetra_stride, b_tv);
   int *dadja = local(ctx, b_adja, (size_t)(4 * ne + 5));
-  unsigned *tcnt = local(ctx, b_tcnt, (size_t)(ne + 1));
-  unsigned *tpos = local(ctx, b_tpos, (size_t)(ne + 1));
-  if (!tv || !dadja || !tcnt || !tpos) return C.fail("hipMalloc"), -1;
+  if (!tv || !dadja) return C.fail("hipMalloc"), -1;
   hipMemcpyAsync(dadja, adja, sizeof(int) * (size_t)(4 * ne + 5), hipMemcpyHostToDevice, s);
-  hipMemsetAsync(tcnt, 0, sizeof(unsigned) * (size_t)(ne + 1), s);
   DevEvent e0, e1;
   e0.create();
   e1.create();
-  hipEventRecord(e0, s);
-  hipLaunchKernelGGL(k_bdry_count, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, dadja, ne, tcnt);
-  if (!C.exclusive_sum(tmp, (const unsigned *)tcnt, tpos, ne + 1, "scan")) return C.fail("scan"), -1;
-  unsigned nt_u = 0;
-  hipMemcpyAsync(&nt_u, tpos + ne, sizeof(unsigned), hipMemcpyDeviceToHost, s);
-  hipStreamSynchronize(s);
-  const int64_t nt = nt_u;
-  if (nt > maxnt) return C.fail("more boundary faces than maxnt"), -1;
-  int *dtria = local(ctx, b_tria, (size_t)(3 * (nt + 1)));
-  if (!dtria) return C.fail("hipMalloc"), -1;
-  hipMemsetAsync(dtria, 0, sizeof(int) * 3, s);
-  hipLaunchKernelGGL(k_bdry_write, dim3(pmx_call::blocks(ne)), dim3(256), 0, s, tv, dadja, ne, tpos, dtria);
-  int *dadjt = nullptr;
-  if (adjt && nt > 0) {
-    unsigned *cnt = local(ctx, b_cnt, (size_t)(np + 2));
-    unsigned *off = local(ctx, b_off, (size_t)(np + 2));
-    int2 *rec = local(ctx, b_rec, (size_t)(3 * nt));
-    int *bof = local(ctx, b_bof, (size_t)(3 * nt));
-    dadjt = local(ctx, b_adjt, (size_t)(3 * nt + 4));
-    if (!cnt || !off || !rec || !bof || !dadjt) return C.fail("hipMalloc"), -1;
-    hipMemsetAsync(cnt, 0, sizeof(unsigned) * (size_t)(np + 2), s);
-    hipMemsetAsync(dadjt, 0, sizeof(int) * (size_t)(3 * nt + 4), s);
-    hipLaunchKernelGGL(k_edge_count, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, dtria, nt, cnt);
-    if (!C.exclusive_sum(tmp2, (const unsigned *)cnt, off, np + 2, "scan")) return C.fail("scan"), -1;
-    hipMemcpyAsync(cnt, off, sizeof(unsigned) * (size_t)(np + 2), hipMemcpyDeviceToDevice, s);
-    hipLaunchKernelGGL(k_edge_scatter, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, dtria, nt, cnt, rec);
-    hipLaunchKernelGGL(k_bucket_of, dim3(pmx_call::blocks(np + 1)), dim3(256), 0, s, off, np + 1, bof);
-    hipLaunchKernelGGL(k_edge_match, dim3(pmx_call::blocks(3 * nt)), dim3(256), 0, s, rec, 3 * nt, off, bof,
-                       dadjt);
-  }
-  hipEventRecord(e1, s);
+  int64_t nt = 0;
+  if (!pmx_bdry_device(C, tv, dadja, 4, -3, ne, np, adjt != nullptr, maxnt, B, &nt, e0, e1)) return -1;
   hipEventSynchronize(e1);
   float ms = 0.f;
   hipEventElapsedTime(&ms, e0, e1);
   ctx->topo_ms = ms;
   if (hipGetLastError() != hipSuccess) return C.fail("launch"), -1;
-  if (hipMemcpy(tria, dtria, sizeof(int) * (size_t)(3 * (nt + 1)), hipMemcpyDeviceToHost) != hipSuccess)
+  if (hipMemcpy(tria, B.tria.p, sizeof(int) * (size_t)(3 * (nt + 1)), hipMemcpyDeviceToHost) != hipSuccess)
     return C.fail("download"), -1;
-  if (dadjt &&
-      hipMemcpy(adjt, dadjt, sizeof(int) * (size_t)(3 * nt + 4), hipMemcpyDeviceToHost) != hipSuccess)
+  if (adjt && nt > 0 &&
+      hipMemcpy(adjt, B.adjt.p, sizeof(int) * (size_t)(3 * nt + 4), hipMemcpyDeviceToHost) != hipSuccess)
     return C.fail("download"), -1;
   return nt;
 }

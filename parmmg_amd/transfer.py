@@ -17,7 +17,10 @@ Names and argument meaning follow the reference:
   (src/metis_pmmg.c) and ``PMMG_fix_contiguity*`` (src/moveinterfaces_pmmg.c).
 * :meth:`Transfer.split_groups`, :meth:`Transfer.split_fetch`,
   :meth:`Transfer.split_release` -- the new groups of ``PMMG_split_eachGrp``
-  (src/grpsplit_pmmg.c).
+  (src/grpsplit_pmmg.c); :meth:`Transfer.split_adopt` makes one of them
+  another context's background on the device (``PMMG_update_oldGrps``,
+  src/libparmmg1.c:653), :meth:`Transfer.download_surface` reads a
+  background's boundary trias back.
 * :meth:`Transfer.merge_groups`, :meth:`Transfer.merge_fetch`,
   :meth:`Transfer.merge_maps`, :meth:`Transfer.merge_adopt`,
   :meth:`Transfer.merge_release` -- ``PMMG_merge_grps``
@@ -97,6 +100,7 @@ class Transfer:
         self.sizes: list[int] = []
         self.bg_np = 0        # vertices of the uploaded background
         self.bg_ne = 0        # ... and its tets
+        self.bg_nt = 0        # ... and its trias
         self.npts = 0
         self.n_new_tets = 0
 
@@ -148,6 +152,7 @@ class Transfer:
         self.sizes = [v.size for v in views[: len(arr)]]
         self.bg_np = m.np
         self.bg_ne = m.ne
+        self.bg_nt = m.nt
 
     def copy_required(self, perm: np.ndarray | None = None, copy_metric: bool = True):
         """pmx_copy_required: frozen (MG_REQ) background points' values into the
@@ -675,6 +680,36 @@ class Transfer:
         self._split_sizes = None
         self._chk(self.lib.pmx_split_release(self.ctx), "pmx_split_release")
 
+    def split_adopt(self, g: int, dst: "Transfer", imet: int = 0, surface: bool = True, hausd: float = 0.01):
+        """Group g of the last split_groups becomes dst's uploaded group on the
+        device (pmx_split_adopt), as dst.upload_background(group mesh,
+        adja=False) of split_fetch(g) would leave it -- with surface the
+        boundary trias and their adjacency are built on the device, without it
+        nt = 0.  This context's plan and background are untouched.  imet:
+        index of the metric among the solutions, or -1."""
+        sz = getattr(self, "_split_sizes", None)
+        if sz is None:                   # before dst changes: its sizes below come from split_groups' table
+            raise RuntimeError("pmx_split_adopt: no plan: call split_groups")
+        r = self.lib.pmx_split_adopt(self.ctx, g, dst.ctx, imet if self.sizes else -1, int(surface), hausd)
+        if not r:
+            raise RuntimeError(f"pmx_split_adopt: {self.lib.pmx_last_error(dst.ctx).decode()}")
+        dst._split_sizes = None
+        dst.sizes = list(self.sizes)
+        dst.bg_ne, dst.bg_np = int(sz[g][0]), int(sz[g][1])
+        dst.bg_nt = int(self.lib.pmx_download_surface(dst.ctx, None, 0, None))   # built on the device
+
+    def download_surface(self):
+        """The installed background's boundary trias as the device holds them
+        (pmx_download_surface): (tria (nt+1, 3), row 0 unused, adjt (3*nt+4,)),
+        the numbering of a surface point's downloaded elem."""
+        nt = self.lib.pmx_download_surface(self.ctx, None, 0, None)      # the size query
+        tria = np.zeros((max(nt, 0) + 1, 3), np.int32)
+        adjt = np.zeros(3 * max(nt, 0) + 4, np.int32)
+        if nt < 0 or self.lib.pmx_download_surface(self.ctx, _ip(tria), nt, _ip(adjt)) != nt:
+            raise RuntimeError(f"pmx_download_surface: {self.lib.pmx_last_error(self.ctx).decode()}")
+        self.bg_nt = int(nt)
+        return tria, adjt
+
     # ---- group merge ----------------------------------------------------------
     def _merge_views(self, groups: list[dict], comm: dict | None = None):
         """The pmx_merge_group array, nsol, the pmx_merge_comm and the numpy
@@ -796,6 +831,7 @@ class Transfer:
         self._split_sizes = None
         self.sizes = list(mg["sol_sizes"])
         self.bg_np, self.bg_ne = int(mg["sizes"][0]), int(mg["sizes"][1])
+        self.bg_nt = 0
 
     def merge_release(self):
         """Free the merge plan's device memory (pmx_merge_release)."""
@@ -947,6 +983,7 @@ class Transfer:
                   "pmx_promote_background")
         self.bg_np = self.npts              # the promoted points are the background's vertices
         self.bg_ne = new_mesh.ne
+        self.bg_nt = new_mesh.nt
         self.npts = 0
 
     def new_mesh_qual(self, tets: np.ndarray | None, opt: int = N.INQUA, dev_ptr: int = 0,
