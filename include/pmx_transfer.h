@@ -36,6 +36,10 @@
  *                                          -> pmx_moveifc_begin / _get_colors /
  *                                             _set_colors / _layer / _marks /
  *                                             _part
+ *   PMMG_check_reachability (src/moveinterfaces_pmmg.c:627-811) -> pmx_reach_face_marks /
+ *                                             pmx_check_reachability; with
+ *   PMMG_fix_contiguity on the displacement's own marks (:1446-1452)
+ *                                          -> pmx_moveifc_fix / pmx_moveifc_reach
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -353,7 +357,11 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * a refusal, after a release and once a background install dropped the state).
  * which = 21: the last pmx_split_adopt into ctx (first to last device
  * operation on ctx's stream; -1 before the first call and after a refused or
- * failed one). */
+ * failed one).
+ * which = 22 / 23: the kernels of the last pmx_check_reachability or
+ * pmx_moveifc_reach, summed / those of the last pmx_moveifc_fix (-1 before the
+ * first call and after a refusal; 23 also once the displacement is gone).  A
+ * pmx_moveifc_fix sets 12 / 13 as pmx_fix_contiguity does. */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -988,6 +996,61 @@ int pmx_moveifc_part(pmx_ctx *ctx, const int32_t *mark, int target, const int *n
                      int32_t *ngrp);
 /* Frees the displacement's device memory (pmx_destroy does too). */
 int pmx_moveifc_release(pmx_ctx *ctx);
+
+/* ---- reachability (PMMG_check_reachability, src/moveinterfaces_pmmg.c:627-811) ----
+ * The call that ends PMMG_part_moveInterfaces after PMMG_fix_contiguity: a
+ * piece of another rank's colour must touch that rank through a face of the
+ * face communicator, or it joins a neighbouring piece.  The exchange of the
+ * colours (step 1, :651-716) stays with the caller; pmx_reach_face_marks
+ * gives what it sends.  The tets' flags the reference carries over from the
+ * fix are a function of the fixed marks: a tet is flagged exactly when its
+ * mark is one of the rank's colours ("Reachability").
+ * Every call below returns 0 without touching its outputs, *counter or the
+ * device's marks when: no group is uploaded; 4 ne >= 2^31; nface < 0 or an
+ * array is NULL with nface > 0; an entry's tet face_index1[i] / 12 lies
+ * outside 1..ne; a colour is listed twice; counter is NULL. */
+typedef struct {
+  int64_t nseeds, nreached, nreached_tets;     /* step 2: entries that seeded (tet unflagged on entry, colour
+                                                  as received), lists flagged, their tets */
+  int64_t nunreached, nmerged, nmerged_tets;   /* step 3: lists met, merged, tets recoloured (a tet counts each time) */
+  int64_t nrescanned, ncannot, counter;        /* merges into an unflagged list; lists with no neighbour outside;
+                                                  *counter at the end */
+  int64_t rounds, relabels, replays, replay_steps;   /* rounds of step 3 (0: nothing was left), labellings after
+                                                  the first, replay launches, tets dequeued */
+} pmx_reach_stats;
+
+/* out[i] = mark[face_index1[i] / 12], i < nface: what the caller puts into
+ * intvalues before the exchange (:664-670).  mark: ne ints, tet k at k-1;
+ * NULL = the live displacement's marks on the device (refused without one). */
+int pmx_reach_face_marks(pmx_ctx *ctx, const int32_t *mark, int64_t nface, const int *face_index1, int32_t *out);
+
+/* Steps 2 and 3 on mark (ne ints, in/out), after pmx_fix_contiguity with the
+ * same colours (NULL = 0..ncolors-1).  color_in[i]: the colour received for
+ * entry i after the discard of :708-716, -1 (PMMG_UNSET) = none.  Step 2:
+ * every unflagged piece that holds the tet of an entry whose colour is the
+ * tet's mark is flagged.  Step 3: the tets are scanned upwards; at an
+ * unflagged tet its piece -- the unflagged tets of its mark, breadth-first,
+ * faces 0..3 -- takes mark and flag of its first neighbour outside the list,
+ * met in list order; without one it stays.  A piece that joined an unflagged
+ * neighbour is met again further up.  *counter: in, the fix's counter; out, the
+ * reference's (ne on a connected mesh).  replay_steps: dequeues per launch of
+ * the list replay, 0 = pmx_fix_contiguity's default.  st may be NULL.
+ * pmx_kernel_ms(ctx, 22): its device time. */
+int pmx_check_reachability(pmx_ctx *ctx, int32_t *mark, int32_t ncolors, const int32_t *colors, int64_t nface,
+                           const int *face_index1, const int32_t *color_in, int64_t *counter, int64_t replay_steps,
+                           pmx_reach_stats *st);
+
+/* The same two calls on the live displacement's marks, in place on the device:
+ * nothing of size ne crosses PCIe, and pmx_moveifc_marks and
+ * pmx_moveifc_part(mark = NULL) return the result.  pmx_moveifc_fix is
+ * pmx_fix_contiguity with the colours nprocs * i + myrank, i < nold_grp;
+ * pmx_moveifc_reach carries its counter on (st->counter) and is refused
+ * without a pmx_moveifc_fix since the last layer, set_colors or reach.  Both
+ * are refused without a live displacement.  The marks change only when the
+ * call succeeds.  pmx_kernel_ms(ctx, 23) / (ctx, 22): their device times. */
+int pmx_moveifc_fix(pmx_ctx *ctx, int64_t replay_steps, pmx_contig_stats *st);
+int pmx_moveifc_reach(pmx_ctx *ctx, int64_t nface, const int *face_index1, const int32_t *color_in,
+                      int64_t replay_steps, pmx_reach_stats *st);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

@@ -146,6 +146,13 @@ class ContigStats(C.Structure):
                                    "replays", "replay_steps")]
 
 
+class ReachStats(C.Structure):
+    """pmx_reach_stats."""
+    _fields_ = [(n, i64) for n in ("nseeds", "nreached", "nreached_tets", "nunreached", "nmerged", "nmerged_tets",
+                                   "nrescanned", "ncannot", "counter", "rounds", "relabels", "replays",
+                                   "replay_steps")]
+
+
 class SplitComm(C.Structure):
     """pmx_split_comm: the old group's internal communicators."""
     _fields_ = [("nface", i64), ("nnode", i64),
@@ -289,6 +296,11 @@ SIGNATURES = {
     "pmx_moveifc_groups": (C.c_int, [C.c_void_p, iptr, iptr]),
     "pmx_moveifc_part": (C.c_int, [C.c_void_p, i32ptr, C.c_int, iptr, i32ptr, i32ptr]),
     "pmx_moveifc_release": (C.c_int, [C.c_void_p]),
+    "pmx_reach_face_marks": (C.c_int, [C.c_void_p, i32ptr, i64, iptr, i32ptr]),
+    "pmx_check_reachability": (C.c_int, [C.c_void_p, i32ptr, C.c_int32, i32ptr, i64, iptr, i32ptr, C.POINTER(i64),
+                                         i64, C.POINTER(ReachStats)]),
+    "pmx_moveifc_fix": (C.c_int, [C.c_void_p, i64, C.POINTER(ContigStats)]),
+    "pmx_moveifc_reach": (C.c_int, [C.c_void_p, i64, iptr, i32ptr, i64, C.POINTER(ReachStats)]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

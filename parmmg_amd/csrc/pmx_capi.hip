@@ -556,6 +556,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && (which == 14 || which == 15 || which == 21)) return pmx_split_kernel_ms(ctx, which);
   if (ctx && which >= 16 && which <= 18) return pmx_merge_kernel_ms(ctx, which);
   if (ctx && (which == 19 || which == 20)) return pmx_moveifc_kernel_ms(ctx, which);
+  if (ctx && (which == 22 || which == 23)) return pmx_reach_kernel_ms(ctx, which);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;

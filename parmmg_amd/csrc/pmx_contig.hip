@@ -41,47 +41,7 @@
 
 namespace {
 
-// control words (d_cctl)
-enum { CC_CHANGED = 0, CC_BADREC = 1, CC_DELETED = 2, CC_ROOTS = 3, CC_PENDING = 4, CC_RERR = 5, CC_NCTL = 8 };
-#define CC_OPEN_BIT 0x80000000u
-#define CC_DEFAULT_REPLAY_STEPS 1024
-
-// parents to self, sizes to 0; a deleted tet raises ctl[CC_DELETED], a
-// neighbour outside 0..ne ctl[CC_BADREC]
-__global__ __launch_bounds__(256) void k_cc_init(const TetRec *__restrict__ tets, int64_t ne, int *__restrict__ par,
-                                                 unsigned *__restrict__ ctl) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k > ne) return;
-  par[k] = (int)k;
-  if (k == 0) return;
-  const int4 *recs = reinterpret_cast<const int4 *>(tets);
-  const int4 v = recs[2 * k], nb = recs[2 * k + 1];
-  if (v.x <= 0) ctl[CC_DELETED] = 1u;
-  const int n = (int)ne;
-  if (nb.x < 0 || nb.x > n || nb.y < 0 || nb.y > n || nb.z < 0 || nb.z > n || nb.w < 0 || nb.w > n)
-    ctl[CC_BADREC] = 1u;
-}
-
-// an ancestor of a that was its own parent when read
-__device__ __forceinline__ int cc_find(const int *par, int a) {
-  int p;
-  while ((p = par[a]) != a) a = p;
-  return a;
-}
-
-// link the trees of a and b: the larger node's parent goes down to the smaller
-// node; when the atomic displaces another parent (or finds a smaller one), the
-// pair (that parent, the smaller node) still has to be linked.  The larger
-// node of the pair strictly decreases, so the loop ends.
-__device__ __forceinline__ void cc_link(int *par, int a, int b) {
-  while (a != b) {
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    const int old = atomicMin(&par[hi], lo);
-    if (old == hi || old == lo) break;
-    a = old;
-    b = lo;
-  }
-}
+#include "pmx_contig_dev.h"   // the control words, cc_find / cc_link, k_cc_init, k_cc_jump
 
 __global__ __launch_bounds__(256) void k_cc_hook(const TetRec *__restrict__ tets, int64_t ne,
                                                  const int *__restrict__ mark, int *par,
@@ -110,15 +70,6 @@ __global__ __launch_bounds__(256) void k_cc_hook(const TetRec *__restrict__ tets
     a = a < b ? a : b;
   }
   if (changed) ctl[CC_CHANGED] = 1u;
-}
-
-// no hooking runs beside it, so roots are stable and every tet ends on its
-// root; nothing to do after a hooking launch that changed nothing
-__global__ __launch_bounds__(256) void k_cc_jump(int64_t ne, int *par, const unsigned *__restrict__ ctl) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x + 1;
-  if (k > ne || !ctl[CC_CHANGED]) return;
-  const int r = cc_find(par, (int)k);
-  if (par[k] != r) par[k] = r;
 }
 
 // per root: size and the open bit in sz[root] (zeroed before); ctl[CC_ROOTS] =
@@ -407,23 +358,19 @@ int pmx_contiguity(pmx_ctx *ctx, const int32_t *part, int32_t nparts, int32_t *c
   return 1;
 }
 
-int pmx_fix_contiguity(pmx_ctx *ctx, int32_t *part, int32_t ncolors, const int32_t *colors, int64_t replay_steps,
-                       pmx_contig_stats *st) {
-  if (!ctx) return 0;
-  hipSetDevice(ctx->device);
-  Contig L{ctx, "pmx_fix_contiguity"};
-  ctx->contig_label_ms = ctx->contig_replay_ms = -1.0;
-  if (!part) { L.fail("part is NULL"); return 0; }
-  if (ncolors < 0 || replay_steps < 0) { L.fail("ncolors < 0 or replay_steps < 0"); return 0; }
-  // colour -> its place in the order
-  std::unordered_map<int, int> place;
-  for (int i = 0; i < ncolors; i++)
-    if (!place.emplace(colors ? colors[i] : i, i).second) { L.fail("duplicate colours"); return 0; }
-  const int steps = (int)std::min<int64_t>(replay_steps ? replay_steps : CC_DEFAULT_REPLAY_STEPS, 1 << 30);
-  if (!L.begin() || !L.set_marks(part) || !L.label()) return 0;
+}  // extern "C"
+
+namespace {
+
+// FIX on the marks in d_cmark (begin() done), colours in the caller's order;
+// steps: dequeues per replay launch
+int fix_marks(Contig &L, int32_t ncolors, const int32_t *colors, const std::unordered_map<int, int> &place,
+              int steps, pmx_contig_stats &S) {
+  pmx_ctx *ctx = L.ctx;
+  if (!L.label()) return 0;
   const int64_t ne = L.ne;
   hipStream_t s = L.s;
-  pmx_contig_stats S{};
+  S = pmx_contig_stats{};
   S.ncomp = (int64_t)L.tab.size();
   if (ne > 0 && hipMemsetAsync(ctx->d_cstamp.p, 0, sizeof(int) * (size_t)(ne + 1), s) != hipSuccess) {
     L.fail("memset");
@@ -536,6 +483,61 @@ int pmx_fix_contiguity(pmx_ctx *ctx, int32_t *part, int32_t ncolors, const int32
     if (hipGetLastError() != hipSuccess) { L.fail("recolour launch"); return 0; }
   }
   S.rounds = L.rounds;
+  return 1;
+}
+
+// colour -> its place in the order; false: a colour listed twice
+bool colour_places(int32_t ncolors, const int32_t *colors, std::unordered_map<int, int> &place) {
+  for (int i = 0; i < ncolors; i++)
+    if (!place.emplace(colors ? colors[i] : i, i).second) return false;
+  return true;
+}
+
+int replay_steps_of(int64_t replay_steps) {
+  return (int)std::min<int64_t>(replay_steps ? replay_steps : CC_DEFAULT_REPLAY_STEPS, 1 << 30);
+}
+
+}  // namespace
+
+int pmx_contig_default_replay_steps() { return CC_DEFAULT_REPLAY_STEPS; }
+
+bool pmx_contig_fix_device(pmx_ctx *ctx, const char *who, int *d_mark, int32_t ncolors, const int32_t *colors,
+                           int64_t replay_steps, pmx_contig_stats *st) {
+  Contig L{ctx, who};
+  ctx->contig_label_ms = ctx->contig_replay_ms = -1.0;
+  if (ncolors < 0 || replay_steps < 0) return L.fail("ncolors < 0 or replay_steps < 0");
+  std::unordered_map<int, int> place;
+  if (!colour_places(ncolors, colors, place)) return L.fail("duplicate colours");
+  if (!L.begin()) return false;
+  const size_t bytes = sizeof(int) * (size_t)(L.ne + 1);
+  if (hipMemcpyAsync(ctx->d_cmark.p, d_mark, bytes, hipMemcpyDeviceToDevice, L.s) != hipSuccess)
+    return L.fail("marks copy");
+  pmx_contig_stats S{};
+  if (!fix_marks(L, ncolors, colors, place, replay_steps_of(replay_steps), S)) return false;
+  if (hipMemcpyAsync(d_mark, ctx->d_cmark.p, bytes, hipMemcpyDeviceToDevice, L.s) != hipSuccess ||
+      hipStreamSynchronize(L.s) != hipSuccess)
+    return L.fail("marks copy");
+  if (st) *st = S;
+  return true;
+}
+
+extern "C" {
+
+int pmx_fix_contiguity(pmx_ctx *ctx, int32_t *part, int32_t ncolors, const int32_t *colors, int64_t replay_steps,
+                       pmx_contig_stats *st) {
+  if (!ctx) return 0;
+  hipSetDevice(ctx->device);
+  Contig L{ctx, "pmx_fix_contiguity"};
+  ctx->contig_label_ms = ctx->contig_replay_ms = -1.0;
+  if (!part) { L.fail("part is NULL"); return 0; }
+  if (ncolors < 0 || replay_steps < 0) { L.fail("ncolors < 0 or replay_steps < 0"); return 0; }
+  std::unordered_map<int, int> place;
+  if (!colour_places(ncolors, colors, place)) { L.fail("duplicate colours"); return 0; }
+  if (!L.begin() || !L.set_marks(part)) return 0;
+  pmx_contig_stats S{};
+  if (!fix_marks(L, ncolors, colors, place, replay_steps_of(replay_steps), S)) return 0;
+  const int64_t ne = L.ne;
+  hipStream_t s = L.s;
   if (ne > 0) {
     std::vector<int32_t> out((size_t)ne);
     if (hipMemcpyAsync(out.data(), ctx->d_cmark.p + 1, sizeof(int32_t) * (size_t)ne, hipMemcpyDeviceToHost, s) !=

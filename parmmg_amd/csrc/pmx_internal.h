@@ -337,6 +337,19 @@ struct pmx_ctx {
   struct pmx_moveifc_state *moveifc = nullptr;
   bool moveifc_valid = false;
   double moveifc_begin_ms = -1.0, moveifc_layer_ms = -1.0;
+  // Reachability (pmx_check_reachability / pmx_moveifc_fix / _reach,
+  // pmx_reach.hip) works on d_cmark with the contiguity's parents, stamps,
+  // queues, table, records and control words; its own: the tets' flags
+  // (ne + 1), per root {seeded, size, start} (3 (ne + 1)), the sorted local
+  // colours, the entries {face_index1 | colour received | gathered marks}, the
+  // decisions {root, mark, flag} of a round.  moveifc_fixed: pmx_moveifc_fix
+  // ran on the live displacement's marks and no layer or set_colors since;
+  // moveifc_counter: its counter.  Device times of the last check / in-place fix
+  DevBuf<int> d_rflag, d_raux, d_rcol, d_rface;
+  DevBuf<int4> d_rdec;
+  bool moveifc_fixed = false;
+  int64_t moveifc_counter = 0;
+  double reach_ms = -1.0, moveifc_fix_ms = -1.0;
   int64_t stat_np = -1;                // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
@@ -517,6 +530,14 @@ template <class R> inline bool read_pub(const pmx_call &C, R &r) {
 // pmx_kernel_ms(ctx, 12 / 13): the labelling / the replay and recolour kernels
 // of the last pmx_contiguity or pmx_fix_contiguity, summed (pmx_contig.hip)
 double pmx_contig_kernel_ms(pmx_ctx *ctx, int which);
+// pmx_fix_contiguity's loop on a device mark array (ne + 1 ints, slot 0
+// unused): staged through d_cmark, written back when the fix succeeded; the
+// dequeues per replay launch that replay_steps = 0 stands for (pmx_contig.hip)
+bool pmx_contig_fix_device(pmx_ctx *ctx, const char *who, int *d_mark, int32_t ncolors, const int32_t *colors,
+                           int64_t replay_steps, pmx_contig_stats *st);
+int pmx_contig_default_replay_steps();
+// pmx_kernel_ms(ctx, 22 / 23): the last reachability check / in-place fix (pmx_reach.hip)
+double pmx_reach_kernel_ms(pmx_ctx *ctx, int which);
 // pmx_kernel_ms(ctx, 14 / 15 / 21): the last split plan / the last fetch / the
 // last pmx_split_adopt into ctx; the plan and its buffers freed (pmx_split.hip)
 double pmx_split_kernel_ms(pmx_ctx *ctx, int which);
@@ -532,6 +553,14 @@ bool pmx_merge_tet_group(pmx_ctx *ctx, const int **tgrp, int64_t *ne);
 // and its buffers freed (pmx_moveifc.hip)
 double pmx_moveifc_kernel_ms(pmx_ctx *ctx, int which);
 void pmx_moveifc_free(pmx_ctx *ctx);
+// the live displacement's marks on the device (ne + 1 ints, slot 0 unused)
+// with its sizes; false: no live displacement (pmx_moveifc.hip)
+struct MoveIfcMarks {
+  int *mark;
+  int64_t ne;
+  int nprocs, myrank, nold;
+};
+bool pmx_moveifc_live_marks(pmx_ctx *ctx, MoveIfcMarks *m);
 // Boundary trias and their edge adjacency of device connectivity tv (1-based
 // int4, slot 0 unused) into B, on C's stream (pmx_topo.hip): a face of a valid
 // tet is a tria when its adjacency entry adj[adj_stride * k + adj_off + f] is 0

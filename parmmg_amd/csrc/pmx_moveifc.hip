@@ -447,7 +447,16 @@ void pmx_moveifc_free(pmx_ctx *ctx) {
   ctx->moveifc = nullptr;
   ctx->moveifc_valid = false;
   ctx->moveifc_begin_ms = ctx->moveifc_layer_ms = -1.0;
+  ctx->moveifc_fixed = false;
+  ctx->moveifc_fix_ms = -1.0;
   delete S;
+}
+
+bool pmx_moveifc_live_marks(pmx_ctx *ctx, MoveIfcMarks *m) {
+  const pmx_moveifc_state *S = ctx->moveifc;
+  if (!S || !ctx->moveifc_valid || !ctx->have_bg) return false;
+  *m = MoveIfcMarks{S->mark.p, S->ne, S->nprocs, S->myrank, S->nold};
+  return true;
 }
 
 double pmx_moveifc_kernel_ms(pmx_ctx *ctx, int which) {
@@ -605,6 +614,7 @@ int pmx_moveifc_set_colors(pmx_ctx *ctx, int64_t n, const int *ip, const int *co
     }
     last[ip[i]] = color[i];
   }
+  ctx->moveifc_fixed = false;           // the next layer moves the marks again
   if (n == 0) return 1;
   const int64_t u = (int64_t)last.size();
   std::vector<int> buf;
@@ -631,6 +641,7 @@ int pmx_moveifc_layer(pmx_ctx *ctx, int64_t seq_steps, pmx_moveifc_stats *stats)
   const size_t nt = (size_t)(ne + 1), npt = (size_t)(np + 1);
   const int nold = S.nold;
   ctx->moveifc_layer_ms = -1.0;
+  ctx->moveifc_fixed = false;
   if (S.layer >= MI_MAX_LAYER) {          // the stamps start again
     PMX_CK(L, hipMemsetAsync(S.pos.p, 0, sizeof(int) * 4 * nt, s));
     S.layer = 0;
@@ -778,11 +789,12 @@ int pmx_moveifc_part(pmx_ctx *ctx, const int32_t *mark, int target, const int *n
   if (target != PMX_GRPSPL_DISTR_TARGET && target != PMX_GRPSPL_MMG_TARGET) { L.fail("unknown target"); return 0; }
   const int64_t ne = S.ne;
   const int nprocs = S.nprocs;
-  std::vector<int32_t> own;
-  if (!mark) {
-    own.resize((size_t)ne);
-    if (!L.down(own.data(), (const int32_t *)S.mark.p + 1, ne) || !L.sync("marks download")) return 0;
-    mark = own.data();
+  if (!mark && ne > 0) {
+    // the device's marks, read where the DMA leaves them: the pinned arena
+    int32_t *h = (int32_t *)pmx_hstage(ctx, sizeof(int32_t) * (size_t)ne);
+    if (!h) return 0;
+    if (!L.down(h, (const int32_t *)S.mark.p + 1, ne) || !L.sync("marks download")) return 0;
+    mark = h;
   }
   std::vector<int32_t> out((size_t)ne);
   if (target == PMX_GRPSPL_MMG_TARGET) {

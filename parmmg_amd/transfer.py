@@ -934,6 +934,75 @@ class Transfer:
                                             part.ctypes.data_as(N.i32ptr), C.byref(n)), "pmx_moveifc_part")
         return part[:ne], n.value
 
+    @staticmethod
+    def _stats(st) -> dict:
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
+    @staticmethod
+    def _faces(face_index1, second=None):
+        fi = np.ascontiguousarray(face_index1, np.int32).ravel()
+        if second is None:
+            return fi, None
+        se = np.ascontiguousarray(second, np.int32).ravel()
+        if se.shape != fi.shape:
+            raise ValueError("face_index1 and color_in differ in length")
+        return fi, se
+
+    def reach_face_marks(self, mark: np.ndarray | None, face_index1) -> np.ndarray:
+        """mark[face_index1 // 12 - 1] gathered on the device
+        (pmx_reach_face_marks): what PMMG_check_reachability sends through the
+        face communicator.  mark: (ne,), None = the live displacement's."""
+        fi, _ = self._faces(face_index1)
+        mk = None if mark is None else np.ascontiguousarray(mark, np.int32)
+        if mk is not None and mk.shape != (self.bg_ne,):
+            raise ValueError(f"mark has shape {mk.shape}, the group has {self.bg_ne} tets")
+        out = np.zeros(max(len(fi), 1), np.int32)
+        self._chk(self.lib.pmx_reach_face_marks(self.ctx, mk.ctypes.data_as(N.i32ptr) if mk is not None else None,
+                                                len(fi), _ip(fi) if fi.size else None,
+                                                out.ctypes.data_as(N.i32ptr)), "pmx_reach_face_marks")
+        return out[:len(fi)]
+
+    def check_reachability(self, mark: np.ndarray, colors_or_n, face_index1, color_in, counter: int,
+                           replay_steps: int = 0):
+        """Steps 2 and 3 of PMMG_check_reachability on a copy of mark, the
+        result of fix_contiguity with the same colours
+        (pmx_check_reachability): (mark, counter, stats).  color_in: the colour
+        received for every entry, -1 = none; counter: the fix's."""
+        ne = self.bg_ne
+        p = np.array(mark, np.int32, order="C")
+        if p.shape != (ne,):
+            raise ValueError(f"mark has shape {p.shape}, the group has {ne} tets")
+        if np.ndim(colors_or_n) == 0:
+            ncol, col = int(colors_or_n), None
+        else:
+            col = np.ascontiguousarray(colors_or_n, np.int32)
+            ncol = len(col)
+        fi, cin = self._faces(face_index1, color_in)
+        cnt, st = C.c_int64(counter), N.ReachStats()
+        self._chk(self.lib.pmx_check_reachability(
+            self.ctx, p.ctypes.data_as(N.i32ptr), ncol, col.ctypes.data_as(N.i32ptr) if col is not None else None,
+            len(fi), _ip(fi) if fi.size else None, cin.ctypes.data_as(N.i32ptr) if fi.size else None,
+            C.byref(cnt), replay_steps, C.byref(st)), "pmx_check_reachability")
+        return p, cnt.value, self._stats(st)
+
+    def moveifc_fix(self, replay_steps: int = 0) -> dict:
+        """PMMG_fix_contiguity on the live displacement's marks, in place on
+        the device (pmx_moveifc_fix): the fields of pmx_contig_stats."""
+        st = N.ContigStats()
+        self._chk(self.lib.pmx_moveifc_fix(self.ctx, replay_steps, C.byref(st)), "pmx_moveifc_fix")
+        return self._stats(st)
+
+    def moveifc_reach(self, face_index1, color_in, replay_steps: int = 0) -> dict:
+        """Steps 2 and 3 of PMMG_check_reachability on the marks moveifc_fix
+        left, in place on the device (pmx_moveifc_reach): the fields of
+        pmx_reach_stats; counter goes on from the fix's."""
+        fi, cin = self._faces(face_index1, color_in)
+        st = N.ReachStats()
+        self._chk(self.lib.pmx_moveifc_reach(self.ctx, len(fi), _ip(fi) if fi.size else None,
+                                             cin.ctypes.data_as(N.i32ptr) if fi.size else None, replay_steps,
+                                             C.byref(st)), "pmx_moveifc_reach")
+        return self._stats(st)
+
     def moveifc_release(self):
         """Free the displacement's device memory (pmx_moveifc_release)."""
         self._moveifc = None
