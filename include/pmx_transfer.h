@@ -40,6 +40,13 @@
  *                                             pmx_check_reachability; with
  *   PMMG_fix_contiguity on the displacement's own marks (:1446-1452)
  *                                          -> pmx_moveifc_fix / pmx_moveifc_reach
+ *   PMMG_part_getInterfaces (src/moveinterfaces_pmmg.c:1150-1212) or Metis's
+ *   part[] after PMMG_fix_contiguity_split (:377-523), handed straight to
+ *   PMMG_split_grps (src/grpsplit_pmmg.c:1680-1711), and the mark
+ *   PMMG_part_getProcs (src/moveinterfaces_pmmg.c:1102-1118) reads off each
+ *   new group                              -> pmx_part_from_marks / _upload /
+ *                                             _download / _fix / _release,
+ *                                             pmx_split_groups_part
  *
  * Rules (ParMmg conventions): plain C, pointers + sizes, no torch types.
  * Host memory is caller owned; device buffers are owned by the context.
@@ -361,7 +368,10 @@ double pmx_topo_ms(pmx_ctx *ctx);
  * which = 22 / 23: the kernels of the last pmx_check_reachability or
  * pmx_moveifc_reach, summed / those of the last pmx_moveifc_fix (-1 before the
  * first call and after a refusal; 23 also once the displacement is gone).  A
- * pmx_moveifc_fix sets 12 / 13 as pmx_fix_contiguity does. */
+ * pmx_moveifc_fix sets 12 / 13 as pmx_fix_contiguity does.
+ * which = 24: the last pmx_part_from_marks (first to last device operation of
+ * the call; -1 before the first call, after a refusal and once the partition
+ * is dropped or replaced by pmx_part_upload). */
 double pmx_kernel_ms(pmx_ctx *ctx, int which);
 /* Forget recorded kernel timings. */
 int    pmx_timing_reset(pmx_ctx *ctx);
@@ -1051,6 +1061,41 @@ int pmx_check_reachability(pmx_ctx *ctx, int32_t *mark, int32_t ncolors, const i
 int pmx_moveifc_fix(pmx_ctx *ctx, int64_t replay_steps, pmx_contig_stats *st);
 int pmx_moveifc_reach(pmx_ctx *ctx, int64_t nface, const int *face_index1, const int32_t *color_in,
                       int64_t replay_steps, pmx_reach_stats *st);
+
+/* ---- the partition on the device, from the marks (or Metis) to the split ----
+ * The context holds at most one partition of the uploaded group: ne ints in
+ * 0..ngrp-1 on the device.  pmx_part_from_marks or pmx_part_upload fills it,
+ * pmx_part_fix repairs it, pmx_split_groups_part splits by it; nothing of size
+ * ne crosses PCIe on the way.  A background upload, a promotion, an adoption
+ * (pmx_split_adopt into this context, pmx_merge_adopt) and pmx_destroy drop
+ * it, as they drop the split plan and the displacement; pmx_moveifc_release
+ * does not.  A refused call leaves its outputs and the held partition as they
+ * were.
+ *
+ * pmx_part_from_marks: PMMG_part_getInterfaces on the live displacement's
+ * marks (refused without one); targets, ngrps_all and refusals as
+ * pmx_moveifc_part(mark = NULL).  *ngrp (may be NULL): the groups.
+ * group_mark (may be NULL, *ngrp ints -- at most nold_grp under the MMG
+ * target, the sum of ngrps_all under DISTR): the mark every tet of group g
+ * carries, nprocs * g + myrank under the MMG target; group_mark[g] % nprocs is
+ * the owner PMMG_part_getProcs reads off the group's first tet.
+ * pmx_kernel_ms(ctx, 24): its device time. */
+int pmx_part_from_marks(pmx_ctx *ctx, int target, const int *ngrps_all, int32_t *ngrp, int32_t *group_mark);
+/* A host partition (Metis's; ne ints, tet k at k-1) becomes the context's.
+ * ngrp < 1 or a value outside 0..ngrp-1 (checked on the device) is refused. */
+int pmx_part_upload(pmx_ctx *ctx, const int32_t *part, int32_t ngrp);
+/* The held partition: part (ne ints) and *ngrp, either may be NULL. */
+int pmx_part_download(pmx_ctx *ctx, int32_t *part, int32_t *ngrp);
+/* PMMG_fix_contiguity_split in place: pmx_fix_contiguity with the colours
+ * 0..ngrp-1.  Sets pmx_kernel_ms(ctx, 12 / 13) as that call does. */
+int pmx_part_fix(pmx_ctx *ctx, int64_t replay_steps, pmx_contig_stats *st);
+/* pmx_split_groups by the held partition (sizes: its ngrp entries): the same
+ * refusals -- "no partition" for "part is NULL" --, the same plan;
+ * pmx_split_fetch and pmx_split_adopt follow. */
+int pmx_split_groups_part(pmx_ctx *ctx, const pmx_split_comm *comm, pmx_split_sizes *sizes, int *tet_new,
+                          int64_t *int_face_nitem, int64_t *int_node_nitem);
+/* Frees the partition's device memory (pmx_destroy does too). */
+int pmx_part_release(pmx_ctx *ctx);
 
 /* PMMG_tetraQual(parmesh, metRidTyp) on the NEW mesh right after the
  * interpolation (src/libparmmg1.c:845, metRidTyp = 1; a size-6 metric

@@ -301,6 +301,13 @@ SIGNATURES = {
                                          i64, C.POINTER(ReachStats)]),
     "pmx_moveifc_fix": (C.c_int, [C.c_void_p, i64, C.POINTER(ContigStats)]),
     "pmx_moveifc_reach": (C.c_int, [C.c_void_p, i64, iptr, i32ptr, i64, C.POINTER(ReachStats)]),
+    "pmx_part_from_marks": (C.c_int, [C.c_void_p, C.c_int, iptr, i32ptr, i32ptr]),
+    "pmx_part_upload": (C.c_int, [C.c_void_p, i32ptr, C.c_int32]),
+    "pmx_part_download": (C.c_int, [C.c_void_p, i32ptr, i32ptr]),
+    "pmx_part_fix": (C.c_int, [C.c_void_p, i64, C.POINTER(ContigStats)]),
+    "pmx_split_groups_part": (C.c_int, [C.c_void_p, C.POINTER(SplitComm), C.POINTER(SplitSizes), iptr,
+                                        C.POINTER(i64), C.POINTER(i64)]),
+    "pmx_part_release": (C.c_int, [C.c_void_p]),
     "pmx_new_mesh_qual": (C.c_int, [C.c_void_p, iptr, i64, i64, C.c_int, C.c_int, dptr, i64, C.c_void_p]),
     "pmx_new_mesh_qual_synced": (C.c_int, [C.c_void_p, C.POINTER(SolView), C.c_int, C.c_int, dptr, i64,
                                           i64, C.c_void_p]),

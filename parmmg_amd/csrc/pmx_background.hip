@@ -129,6 +129,7 @@ int env_sample_mode() {
 void begin_background(pmx_ctx *ctx, bool layout_env) {
   ctx->have_bg = ctx->ran = ctx->have_derived = ctx->have_tetv = ctx->have_qual = false;
   ctx->have_pmap = ctx->split_valid = ctx->moveifc_valid = false;
+  pmx_part_drop(ctx);
   ctx->have_ptag = ctx->have_csr = ctx->have_surf = ctx->fan_rot = ctx->bg_btv = false;
   ctx->stat_np = -1;
   ctx->eager_nch = 0;

@@ -66,6 +66,7 @@ pmx_ctx::~pmx_ctx() {
   pmx_split_free(this);
   pmx_merge_free(this);
   pmx_moveifc_free(this);
+  pmx_part_drop(this);
 }
 
 extern "C" {
@@ -557,6 +558,7 @@ double pmx_kernel_ms(pmx_ctx *ctx, int which) {
   if (ctx && which >= 16 && which <= 18) return pmx_merge_kernel_ms(ctx, which);
   if (ctx && (which == 19 || which == 20)) return pmx_moveifc_kernel_ms(ctx, which);
   if (ctx && (which == 22 || which == 23)) return pmx_reach_kernel_ms(ctx, which);
+  if (ctx && which == 24) return pmx_part_kernel_ms(ctx);
   if (!ctx || ctx->ev_used == 0 || which < 0 || which > 6) return -1.0;
   hipStreamSynchronize(ctx->stream);
   double tot = 0.0;

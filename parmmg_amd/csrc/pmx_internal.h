@@ -133,6 +133,24 @@ struct NewTets {
   int4 *grow_htets(int64_t ne);         // h for ne + 1 records (ev already waited for)
 };
 
+// The context's partition (pmx_part_*, pmx_part.hip): what the displacement's
+// marks or the host's Metis array stand for, between the fix and the split.
+// part: ne + 1 ints, tet k at k, as pmx_split_plan reads it; next: the one a
+// call builds, swapped in when the call succeeded, so that a refusal leaves
+// the held partition alone (and the scratch of pmx_moveifc_part(mark = NULL));
+// tab: the colour table of the DISTR target -- sum (nprocs + 1), then the used
+// flags that become the pack map; ctl: {bad marks, the smallest offending tet}.
+// group_mark[g]: the mark of every tet of group g, empty after an upload.
+struct pmx_partition {
+  DevBuf<int> part, next, tab;
+  DevBuf<unsigned> ctl;
+  std::vector<int> group_mark;
+  int ngrp = 0;
+  bool valid = false;
+  DevEvent ev[2];
+  double ms = -1.0;                     // pmx_kernel_ms(ctx, 24)
+};
+
 struct pmx_ctx {
   int device = 0;
   hipStream_t own = nullptr, stream = nullptr;
@@ -350,6 +368,9 @@ struct pmx_ctx {
   bool moveifc_fixed = false;
   int64_t moveifc_counter = 0;
   double reach_ms = -1.0, moveifc_fix_ms = -1.0;
+  // The partition (pmx_part.hip), valid until the next background upload,
+  // promotion or adoption (pmx_part_drop); pmx_moveifc_release leaves it
+  pmx_partition partition;
   int64_t stat_np = -1;                // node count of pmx_count_nodes (-1: np)
   DevBuf<uint8_t> d_touch;
   DevBuf<int> d_cidx, d_intv;
@@ -559,8 +580,26 @@ struct MoveIfcMarks {
   int *mark;
   int64_t ne;
   int nprocs, myrank, nold;
+  const int *displs;         // the map's displsgrp (host, nprocs + 1 ints)
 };
 bool pmx_moveifc_live_marks(pmx_ctx *ctx, MoveIfcMarks *m);
+// pmx_kernel_ms(ctx, 24): the last pmx_part_from_marks (pmx_part.hip)
+double pmx_part_kernel_ms(pmx_ctx *ctx);
+// the held partition is no more: called by begin_background, that is by every
+// install that drops the split plan and the displacement, and by the
+// context's destructor (pmx_part.hip)
+void pmx_part_drop(pmx_ctx *ctx);
+// PMMG_part_getInterfaces on the live displacement's marks into dst (grown to
+// ne + 1 ints, tet k at k) on the context's stream, which is synchronised.
+// The held partition is not read or written: pmx_part_from_marks swaps dst in,
+// pmx_moveifc_part(mark = NULL) downloads it.  group_mark: resized to *ngrp;
+// ms (may be null): first to last device operation.  false + ctx->err, and
+// dst's contents are undefined (pmx_part.hip)
+bool pmx_part_of_marks(pmx_ctx *ctx, const char *who, int target, const int *ngrps_all, DevBuf<int> &dst,
+                       int *ngrp, std::vector<int> &group_mark, double *ms);
+// the held partition on the device (ne + 1 ints, tet k at k) and its group
+// count; false: none (pmx_part.hip)
+bool pmx_part_held(pmx_ctx *ctx, const int **part, int *ngrp);
 // Boundary trias and their edge adjacency of device connectivity tv (1-based
 // int4, slot 0 unused) into B, on C's stream (pmx_topo.hip): a face of a valid
 // tet is a tria when its adjacency entry adj[adj_stride * k + adj_off + f] is 0

@@ -455,7 +455,7 @@ void pmx_moveifc_free(pmx_ctx *ctx) {
 bool pmx_moveifc_live_marks(pmx_ctx *ctx, MoveIfcMarks *m) {
   const pmx_moveifc_state *S = ctx->moveifc;
   if (!S || !ctx->moveifc_valid || !ctx->have_bg) return false;
-  *m = MoveIfcMarks{S->mark.p, S->ne, S->nprocs, S->myrank, S->nold};
+  *m = MoveIfcMarks{S->mark.p, S->ne, S->nprocs, S->myrank, S->nold, S->displs.data()};
   return true;
 }
 
@@ -789,12 +789,21 @@ int pmx_moveifc_part(pmx_ctx *ctx, const int32_t *mark, int target, const int *n
   if (target != PMX_GRPSPL_DISTR_TARGET && target != PMX_GRPSPL_MMG_TARGET) { L.fail("unknown target"); return 0; }
   const int64_t ne = S.ne;
   const int nprocs = S.nprocs;
-  if (!mark && ne > 0) {
-    // the device's marks, read where the DMA leaves them: the pinned arena
-    int32_t *h = (int32_t *)pmx_hstage(ctx, sizeof(int32_t) * (size_t)ne);
-    if (!h) return 0;
-    if (!L.down(h, (const int32_t *)S.mark.p + 1, ne) || !L.sync("marks download")) return 0;
-    mark = h;
+  if (!mark) {
+    // the device's marks: the partition's kernels into its scratch (the held
+    // partition stays as it is), then one download through the pinned arena
+    DevBuf<int> &d = ctx->partition.next;
+    std::vector<int> group_mark;
+    int n = 0;
+    if (!pmx_part_of_marks(ctx, L.who, target, ngrps_all, d, &n, group_mark, nullptr)) return 0;
+    if (ne > 0) {
+      const int32_t *h = (const int32_t *)pmx_hstage(ctx, sizeof(int32_t) * (size_t)ne);
+      if (!h) return 0;
+      if (!L.down((int32_t *)h, (const int32_t *)d.p + 1, ne) || !L.sync("part download")) return 0;
+      par_for(0, ne, [&](int64_t a, int64_t b) { std::copy(h + a, h + b, part + a); });
+    }
+    if (ngrp) *ngrp = n;
+    return 1;
   }
   std::vector<int32_t> out((size_t)ne);
   if (target == PMX_GRPSPL_MMG_TARGET) {

@@ -458,7 +458,10 @@ struct Split : pmx_call {
            sync("group table");
   }
 
-  bool plan(const int32_t *part, int ngrp, const pmx_split_comm *comm);
+  // part: the host's array (ne ints), uploaded into the plan's buffer; NULL:
+  // dpart, a partition on the device (ne + 1 ints, tet k at k), read where it
+  // lies -- the plan only reads the partition, and only while it is built
+  bool plan(const int32_t *part, const int *dpart, int ngrp, const pmx_split_comm *comm);
 };
 
 static int bits_for(u64 maxval) {
@@ -467,7 +470,7 @@ static int bits_for(u64 maxval) {
   return b;
 }
 
-bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
+bool Split::plan(const int32_t *part, const int *dpart, int ngrp, const pmx_split_comm *comm) {
   pmx_split_plan &P = *pl;
   const int64_t ne = ctx->ne, np = ctx->np, nq = 4 * ne;
   const TetRec *tets = ctx->d_tets.p;
@@ -481,7 +484,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   P.ngrp = ngrp;
   P.gt.assign((size_t)GT_ROWS * G1, 0);
   const size_t n1 = (size_t)(ne + 1);
-  if (!pmx_dgrow(ctx, P.part, n1) || !pmx_dgrow(ctx, P.iota, n1) || !pmx_dgrow(ctx, P.tcat, n1) ||
+  if ((part && !pmx_dgrow(ctx, P.part, n1)) || !pmx_dgrow(ctx, P.iota, n1) || !pmx_dgrow(ctx, P.tcat, n1) ||
       !pmx_dgrow(ctx, P.tnew, n1) || !pmx_dgrow(ctx, P.gcat, n1) || !pmx_dgrow(ctx, P.ctl, SC_NCTL) ||
       !pmx_dgrow(ctx, P.gtab, (size_t)GT_ROWS * G1) || !pmx_dgrow(ctx, P.first, (size_t)(np + 1)) ||
       !pmx_dgrow(ctx, P.mincut, (size_t)(np + 1)) || !pmx_dgrow(ctx, P.newval, (size_t)(np + 1)) ||
@@ -494,9 +497,10 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   if (!ok(hipEventRecord(P.ev[0], s), "event record")) return false;
   if (!ok(hipMemsetAsync(P.ctl.p, 0, sizeof(unsigned) * SC_NCTL, s), "memset") ||
       !ok(hipMemsetAsync(P.gtab.p, 0, sizeof(int) * (size_t)GT_ROWS * G1, s), "memset") ||
-      !ok(hipMemcpyAsync(P.part.p + 1, part, sizeof(int) * (size_t)ne, hipMemcpyHostToDevice, s), "part upload"))
+      (part && !ok(hipMemcpyAsync(P.part.p + 1, part, sizeof(int) * (size_t)ne, hipMemcpyHostToDevice, s), "part upload")))
     return false;
-  hipLaunchKernelGGL(k_sp_check, dim3(blocks(ne)), dim3(256), 0, s, tets, ne, np, (const int *)P.part.p, ngrp,
+  if (part) dpart = P.part.p;
+  hipLaunchKernelGGL(k_sp_check, dim3(blocks(ne)), dim3(256), 0, s, tets, ne, np, dpart, ngrp,
                      P.iota.p, P.ctl.p);
   if (!read_ctl(h)) return false;
   if (h[SC_DELETED]) return fail("a deleted tet (v[0] <= 0): the reference wants a packed mesh");
@@ -521,7 +525,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   }
 
   // tets: the stable order by part
-  if (!sort_pairs(P.tmp, (const unsigned *)(P.part.p + 1), P.gcat.p, (const int *)P.iota.p, P.tcat.p, ne,
+  if (!sort_pairs(P.tmp, (const unsigned *)(dpart + 1), P.gcat.p, (const int *)P.iota.p, P.tcat.p, ne,
                   bits_for((u64)ngrp), "tet sort"))
     return false;
   int *gt = P.gtab.p;
@@ -589,7 +593,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
   {
     // mincut: 0x7f7f7f7f, above every group number
     if (!ok(hipMemsetAsync(P.mincut.p, 0x7f, sizeof(int) * (size_t)(np + 1), s), "memset")) return false;
-    RemapArgs a{tets, P.tcat.p, P.gcat.p, P.part.p, P.tnew.p, gt, gt + GT_P * G1, have_f ? P.fold.p : nullptr, ne,
+    RemapArgs a{tets, P.tcat.p, P.gcat.p, dpart, P.tnew.p, gt, gt + GT_P * G1, have_f ? P.fold.p : nullptr, ne,
                 Lookup{P.first.p, P.gcat.p, P.rank.p, P.skey2.p, P.sval.p, nside},
                 P.vcat.p, P.acat.p, P.fl.p, P.ckey.p, P.mincut.p, P.ctl.p};
     hipLaunchKernelGGL(k_sp_remap, dim3(blocks(ne)), dim3(256), 0, s, a);
@@ -638,7 +642,7 @@ bool Split::plan(const int32_t *part, int ngrp, const pmx_split_comm *comm) {
     return fail("a communicator position >= 2^31");
   if (!pmx_dgrow(ctx, P.f1, (size_t)P.NF + 1) || !pmx_dgrow(ctx, P.f2, (size_t)P.NF + 1)) return false;
   {
-    FaceArgs a{tets, P.tcat.p, P.gcat.p, P.part.p, P.tnew.p, gt, have_f ? P.fold.p : nullptr,
+    FaceArgs a{tets, P.tcat.p, P.gcat.p, dpart, P.tnew.p, gt, have_f ? P.fold.p : nullptr,
                have_f ? P.in_f1.p : nullptr, have_f ? P.in_f2.p : nullptr, ne, P.fl.p, P.epos.p, P.opos.p, (int)fn0,
                P.f1.p, P.f2.p};
     hipLaunchKernelGGL(k_sp_faces, dim3(blocks(ne)), dim3(256), 0, s, a);
@@ -672,20 +676,27 @@ double pmx_split_kernel_ms(pmx_ctx *ctx, int which) {
   return which == 14 ? ctx->split_plan_ms : which == 15 ? ctx->split_fetch_ms : ctx->split_adopt_ms;
 }
 
-extern "C" {
-
-int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_split_comm *comm,
-                     pmx_split_sizes *sizes, int *tet_new, int64_t *int_face_nitem, int64_t *int_node_nitem) {
+// pmx_split_groups and pmx_split_groups_part: part, the host's array, or --
+// device -- the context's partition (ngrp is then the partition's)
+static int split_groups(pmx_ctx *ctx, const char *who, const int32_t *part, bool device, int32_t ngrp,
+                        const pmx_split_comm *comm, pmx_split_sizes *sizes, int *tet_new, int64_t *int_face_nitem,
+                        int64_t *int_node_nitem) {
   if (!ctx) return 0;
   hipSetDevice(ctx->device);
   ctx->split_valid = false;
   ctx->split_plan_ms = ctx->split_fetch_ms = -1.0;
   if (!ctx->split) ctx->split = new pmx_split_plan();
-  Split S{ctx, "pmx_split_groups"};
+  Split S{ctx, who};
   if (!ctx->have_bg) { S.fail("upload a group first"); return 0; }
   const int64_t ne = ctx->ne, np = ctx->np;
   if (4 * ne >= (1LL << 31)) { S.fail("4 ne >= 2^31 (32-bit indices)"); return 0; }
-  if (!part) { S.fail("part is NULL"); return 0; }
+  const int *dpart = nullptr;
+  if (device) {
+    if (!pmx_part_held(ctx, &dpart, &ngrp)) {
+      S.fail("no partition: call pmx_part_from_marks or pmx_part_upload");
+      return 0;
+    }
+  } else if (!part) { S.fail("part is NULL"); return 0; }
   if (ngrp < 1) { S.fail("ngrp < 1"); return 0; }
   if ((int64_t)ngrp > ne) { S.fail("more parts than tets: a part is empty"); return 0; }
   if (comm) {
@@ -706,7 +717,7 @@ int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_
         return 0;
       }
   }
-  if (!S.plan(part, ngrp, comm)) return 0;
+  if (!S.plan(part, dpart, ngrp, comm)) return 0;
   const pmx_split_plan &P = *ctx->split;
   std::vector<int> tn;
   if (tet_new) {
@@ -729,6 +740,19 @@ int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_
   if (int_node_nitem) *int_node_nitem = (comm ? comm->int_node_nitem : 0) + P.NN;
   ctx->split_valid = true;
   return 1;
+}
+
+extern "C" {
+
+int pmx_split_groups(pmx_ctx *ctx, const int32_t *part, int32_t ngrp, const pmx_split_comm *comm,
+                     pmx_split_sizes *sizes, int *tet_new, int64_t *int_face_nitem, int64_t *int_node_nitem) {
+  return split_groups(ctx, "pmx_split_groups", part, false, ngrp, comm, sizes, tet_new, int_face_nitem, int_node_nitem);
+}
+
+int pmx_split_groups_part(pmx_ctx *ctx, const pmx_split_comm *comm, pmx_split_sizes *sizes, int *tet_new,
+                          int64_t *int_face_nitem, int64_t *int_node_nitem) {
+  return split_groups(ctx, "pmx_split_groups_part", nullptr, true, 0, comm, sizes, tet_new, int_face_nitem,
+                      int_node_nitem);
 }
 
 int pmx_split_fetch(pmx_ctx *ctx, int32_t g, const pmx_split_out *out) {

@@ -607,17 +607,9 @@ class Transfer:
                                               replay_steps, C.byref(st)), "pmx_fix_contiguity")
         return p, {f: getattr(st, f) for f, _ in st._fields_}
 
-    def split_groups(self, part: np.ndarray, ngrp: int, comm: dict | None = None) -> dict:
-        """PMMG_split_eachGrp of the uploaded (or promoted) group by part
-        (pmx_split_groups): the plan stays on the device, split_fetch returns
-        one group.  comm: the old group's internal communicators, any of
-        face_index1/2, node_index1/2, int_face_nitem, int_node_nitem.  Returns
-        sizes ((ngrp, 4) int64: ne, np, nface, nnode per group), tet_new (ne,)
-        and the two final nitem."""
-        ne = self.bg_ne
-        p = np.ascontiguousarray(part, np.int32)
-        if p.shape != (ne,):
-            raise ValueError(f"part has shape {p.shape}, the group has {ne} tets")
+    @staticmethod
+    def _split_comm(comm: dict | None):
+        """comm as a pmx_split_comm, with the arrays it points into."""
         comm = comm or {}
         arr = {k: np.ascontiguousarray(comm.get(k, np.zeros(0)), np.int32)
                for k in ("face_index1", "face_index2", "node_index1", "node_index2")}
@@ -629,6 +621,20 @@ class Transfer:
             setattr(c, k, _ip(a) if a.size else None)
         c.int_face_nitem = int(comm.get("int_face_nitem", 0))
         c.int_node_nitem = int(comm.get("int_node_nitem", 0))
+        return c, arr
+
+    def split_groups(self, part: np.ndarray, ngrp: int, comm: dict | None = None) -> dict:
+        """PMMG_split_eachGrp of the uploaded (or promoted) group by part
+        (pmx_split_groups): the plan stays on the device, split_fetch returns
+        one group.  comm: the old group's internal communicators, any of
+        face_index1/2, node_index1/2, int_face_nitem, int_node_nitem.  Returns
+        sizes ((ngrp, 4) int64: ne, np, nface, nnode per group), tet_new (ne,)
+        and the two final nitem."""
+        ne = self.bg_ne
+        p = np.ascontiguousarray(part, np.int32)
+        if p.shape != (ne,):
+            raise ValueError(f"part has shape {p.shape}, the group has {ne} tets")
+        c, _keep = self._split_comm(comm)
         sizes = (N.SplitSizes * max(ngrp, 1))()
         tet_new = np.zeros(ne, np.int32)
         fn, nn = C.c_int64(0), C.c_int64(0)
@@ -861,7 +867,8 @@ class Transfer:
         self._moveifc = None
         self._chk(self.lib.pmx_moveifc_begin(self.ctx, tg.ctypes.data_as(N.i32ptr) if tg is not None else None,
                                              C.byref(mp), C.byref(nf)), "pmx_moveifc_begin")
-        self._moveifc = {"nold_grp": mp.nold_grp, "nprocs": nprocs, "myrank": myrank, "ne": ne, "np": self.bg_np}
+        self._moveifc = {"nold_grp": mp.nold_grp, "nprocs": nprocs, "myrank": myrank, "ne": ne, "np": self.bg_np,
+                         "ngrps_all": int(displs[-1])}
         return nf.value
 
     def _moveifc_state(self) -> dict:
@@ -1007,6 +1014,70 @@ class Transfer:
         """Free the displacement's device memory (pmx_moveifc_release)."""
         self._moveifc = None
         self._chk(self.lib.pmx_moveifc_release(self.ctx), "pmx_moveifc_release")
+
+    # ---- the partition on the device ------------------------------------------------
+    def part_from_marks(self, target: int = N.GRPSPL_MMG_TARGET, ngrps_all=None):
+        """PMMG_part_getInterfaces on the live displacement's marks, kept on
+        the device (pmx_part_from_marks): (ngrp, group_mark).  group_mark[g] is
+        the mark every tet of group g carries; group_mark % nprocs are the
+        owners PMMG_part_getProcs reads."""
+        st = self._moveifc_state()
+        ng = None if ngrps_all is None else np.ascontiguousarray(ngrps_all, np.int32)
+        if ng is not None and len(ng) != st["nprocs"]:
+            raise ValueError("ngrps_all wants nprocs entries")
+        # as many groups as colours at the most
+        cap = max(st["nold_grp"], int(ng.clip(0).sum()) if ng is not None else st.get("ngrps_all", 0), 1)
+        gm = np.zeros(cap, np.int32)
+        n = C.c_int32(0)
+        self._chk(self.lib.pmx_part_from_marks(self.ctx, target, _ip(ng) if ng is not None else None, C.byref(n),
+                                               gm.ctypes.data_as(N.i32ptr)), "pmx_part_from_marks")
+        return n.value, gm[:n.value].copy()
+
+    def part_upload(self, part: np.ndarray, ngrp: int):
+        """A host partition (Metis's) becomes the device's (pmx_part_upload)."""
+        p = np.ascontiguousarray(part, np.int32)
+        if p.shape != (self.bg_ne,):
+            raise ValueError(f"part has shape {p.shape}, the group has {self.bg_ne} tets")
+        self._chk(self.lib.pmx_part_upload(self.ctx, p.ctypes.data_as(N.i32ptr) if p.size else None, ngrp),
+                  "pmx_part_upload")
+
+    def part_download(self):
+        """The device's partition (pmx_part_download): (part (ne,), ngrp)."""
+        ne = self.bg_ne
+        part = np.zeros(max(ne, 1), np.int32)
+        n = C.c_int32(0)
+        self._chk(self.lib.pmx_part_download(self.ctx, part.ctypes.data_as(N.i32ptr), C.byref(n)),
+                  "pmx_part_download")
+        return part[:ne], n.value
+
+    def part_fix(self, replay_steps: int = 0) -> dict:
+        """PMMG_fix_contiguity_split on the device's partition, in place
+        (pmx_part_fix): the fields of pmx_contig_stats."""
+        st = N.ContigStats()
+        self._chk(self.lib.pmx_part_fix(self.ctx, replay_steps, C.byref(st)), "pmx_part_fix")
+        return self._stats(st)
+
+    def split_groups_part(self, comm: dict | None = None) -> dict:
+        """split_groups by the device's partition (pmx_split_groups_part): the
+        same dict."""
+        ne = self.bg_ne
+        n = C.c_int32(0)
+        # without a partition the library refuses the split itself
+        ngrp = n.value if self.lib.pmx_part_download(self.ctx, None, C.byref(n)) else 0
+        c, _keep = self._split_comm(comm)
+        sizes = (N.SplitSizes * max(ngrp, 1))()
+        tet_new = np.zeros(ne, np.int32)
+        fn, nn = C.c_int64(0), C.c_int64(0)
+        self._split_sizes = None
+        self._chk(self.lib.pmx_split_groups_part(self.ctx, C.byref(c), sizes, _ip(tet_new) if ne else None,
+                                                 C.byref(fn), C.byref(nn)), "pmx_split_groups_part")
+        sz = np.array([[s.ne, s.np, s.nface, s.nnode] for s in sizes[:ngrp]], np.int64).reshape(ngrp, 4)
+        self._split_sizes = sz
+        return {"sizes": sz, "tet_new": tet_new, "int_face_nitem": fn.value, "int_node_nitem": nn.value}
+
+    def part_release(self):
+        """Free the partition's device memory (pmx_part_release)."""
+        self._chk(self.lib.pmx_part_release(self.ctx), "pmx_part_release")
 
     def move_interfaces(self, tet_group, map: dict, nlayers: int = 2, exchange=None, node_points=None):
         """PMMG_part_moveInterfaces: begin and nlayers layers.  exchange(colors)
