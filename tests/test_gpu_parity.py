@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import reference_locate as RL
 from conftest import REF_INPUTS
 from helpers import bits_equal, compare_exact, compare_volume, cube_case, lin_field
 from oracle import oracle as O
@@ -301,6 +302,9 @@ def test_tie_points_canonical(transfer, flags):
     for i in range(len(x)):
         cont = [k for k in range(1, m.ne + 1) if o.tet_contains(k, x[i])[0]]
         assert cont and r.elem[i] == min(cont), (i, r.elem[i], cont)
+    # ... and by the long-double definition, which shares nothing with the oracle's predicate
+    rep = RL.check_volume(m, x, r.elem, r.status, True)
+    assert not rep["violations"] and rep["undecidable"] == 0 and rep["ties"] > 150, rep["violations"][:5]
     outs, elem, st, *_ = o.interp(x, t, sols, imet=0)
     c = compare_volume(o, x, t, (r.sols, r.elem, r.status), (outs, elem, st), sols)
     assert c["ties"] > 0
