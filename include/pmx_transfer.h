@@ -870,12 +870,62 @@ typedef struct { int64_t np, ne, nnode, nface; } pmx_merge_sizes;
 int pmx_merge_groups(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_group *groups, int nsol,
                      const pmx_merge_comm *comm, pmx_merge_sizes *sizes);
 
+/* One source of a merge.  held == NULL: host views, exactly as
+ * pmx_merge_groups reads g.  held != NULL: the points, tets and solutions are
+ * those of the group that context holds as its background (uploaded, promoted,
+ * split-adopted or merge-adopted) on ctx's device; of g only nnode, nface and
+ * the four index arrays are read, in the held group's own numbering. */
+typedef struct { pmx_ctx *held; pmx_merge_group g; } pmx_merge_source;
+
+/* pmx_merge_groups with sources that contexts hold: both merges of
+ * PMMG_split_n2mGrps (src/loadbalancing_pmmg.c:88,135) find their groups on
+ * the device -- the remeshed groups promoted after the interpolation step, the
+ * DISTR split's stayers one pmx_split_adopt away --, and only the groups MPI
+ * delivered are host views.  Host and held sources mix in one call; ctx may be
+ * a source, and a context may be named twice.  Of a held group nothing crosses
+ * PCIe but its index arrays and a few control words: device kernels read its
+ * vertex rows, connectivity and interleaved solution rows in place.
+ *
+ * A held group need not be packed (after MMG5_mmg3d1_delone the reference
+ * packs the tets only, MMG5_paktet, src/libparmmg1.c:769).  A point that no
+ * valid tet (v[0] > 0) of the group holds is dropped, as PMMG_merge_grps skips
+ * !MG_VOK (src/mergemesh_pmmg.c:346,507); a deleted tet is dropped (:710); the
+ * survivors keep their order, which is how PMMG_mark_packedTetra
+ * (src/libparmmg1.c:102-113) and the points' tmp (:245-248) number a packed
+ * group.  The result is pmx_merge_groups of the stably packed groups with the
+ * ids mapped back: tet_old and point_old of the fetch are ids in the held
+ * group's own numbering, pmx_merge_maps(g) is sized by its own np_g and ne_g
+ * and holds 0 for a dropped point or tet, node_index1 / face_index1 are given
+ * in its own numbering.  A deliberate difference: group 0 is compacted like
+ * the others -- the reference fills group 0's holes through Mmg's free list
+ * while it appends the other groups' entities, a numbering the library has
+ * never reproduced; a packed group 0 gives the reference's numbering.  Host
+ * sources keep pmx_merge_groups' contract: a deleted tet is refused, every
+ * point is merged.
+ *
+ * The plan is an ordinary merge plan: pmx_merge_fetch, _maps, _adopt,
+ * _release, pmx_moveifc_begin(tet_group = NULL) and the timing slots 16 to 18
+ * work on it (slot 16: first to last device operation of this call).  ctx's
+ * stream waits for each holder's; the call returns when its copies are done,
+ * so a holder may be re-uploaded or destroyed right after.
+ * Returns 0 (pmx_last_error(ctx), naming the group), sizes and every holder
+ * untouched and no plan left: everything pmx_merge_groups refuses, for a held
+ * group found by the device; sources NULL; a holder without a background, on
+ * another device, with another nsol or other solution sizes than the call's
+ * (those of the first source); a node or face entry that names a dropped point
+ * or tet (the reference asserts, :59, :622); a holder whose points are all
+ * dropped. */
+int pmx_merge_groups_from(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_source *sources, int nsol,
+                          const pmx_merge_comm *comm, pmx_merge_sizes *sizes);
+
 /* The merged group's arrays, sized by the plan's sizes; every pointer may be
  * NULL (not fetched):
  *   tetra_v        4*(ne+1) ints, Mmg layout: rows 1..ne written
  *   tet_group      ne ints: the group merged tet j came from, at j-1 (what
  *                  PMMG_set_color_tetra leaves in mark)
- *   tet_old        ne ints: its local id in that group
+ *   tet_old        ne ints: its local id in that group (a held source of
+ *                  pmx_merge_groups_from: in the held group's own numbering;
+ *                  point_old likewise)
  *   point_group    np ints: the group whose copy created merged point i, at i-1
  *   point_old      np ints: that copy's local id
  *   xyz            3*(np+1) doubles, rows 1..np written: the creating copy's
@@ -898,7 +948,9 @@ int pmx_merge_fetch(pmx_ctx *ctx, const pmx_merge_out *out);
 
 /* Group g's local-to-merged maps: point_new (np_g ints, local point k at k-1:
  * meshJ->point[k].tmp) and tet_new (ne_g ints: tetra[k].flag); either may be
- * NULL.  Returns 0, the arrays untouched: no plan; g outside 0..ngrp-1. */
+ * NULL.  After pmx_merge_groups_from np_g and ne_g are the source's own sizes
+ * (a held group's, unused points and deleted tets counted: their entries are
+ * 0).  Returns 0, the arrays untouched: no plan; g outside 0..ngrp-1. */
 int pmx_merge_maps(pmx_ctx *ctx, int32_t g, int *point_new, int *tet_new);
 
 /* The merged group becomes the context's uploaded group without crossing

@@ -180,6 +180,11 @@ class MergeGroup(C.Structure):
                 ("node_index1", iptr), ("node_index2", iptr), ("face_index1", iptr), ("face_index2", iptr)]
 
 
+class MergeSource(C.Structure):
+    """pmx_merge_source: a context that holds the group (NULL: host views), and the group."""
+    _fields_ = [("held", C.c_void_p), ("g", MergeGroup)]
+
+
 class MergeComm(C.Structure):
     """pmx_merge_comm: the internal communicators' nitem and the external ones (CSR)."""
     _fields_ = [("int_node_nitem", i64), ("int_face_nitem", i64), ("next_node", C.c_int32), ("next_face", C.c_int32),
@@ -283,6 +288,8 @@ SIGNATURES = {
     "pmx_download_surface": (C.c_int64, [C.c_void_p, iptr, i64, iptr]),
     "pmx_merge_groups": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MergeGroup), C.c_int, C.POINTER(MergeComm),
                                    C.POINTER(MergeSizes)]),
+    "pmx_merge_groups_from": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(MergeSource), C.c_int, C.POINTER(MergeComm),
+                                        C.POINTER(MergeSizes)]),
     "pmx_merge_fetch": (C.c_int, [C.c_void_p, C.POINTER(MergeOut)]),
     "pmx_merge_maps": (C.c_int, [C.c_void_p, C.c_int32, iptr, iptr]),
     "pmx_merge_adopt": (C.c_int, [C.c_void_p, C.c_int]),

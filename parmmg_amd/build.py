@@ -29,6 +29,7 @@ HIP_SOURCES = ["pmx_capi.hip", "pmx_points.hip", "pmx_results.hip", "pmx_hostpoo
                "pmx_kernels.hip", "pmx_walk.hip", "pmx_bdy.hip", "pmx_fans.hip", "pmx_seq.hip",
                "pmx_quality.hip", "pmx_lengths.hip", "pmx_graph.hip", "pmx_reduce.hip", "pmx_groups.hip",
                "pmx_topo.hip", "pmx_medit.hip", "pmx_more.hip", "pmx_contig.hip", "pmx_split.hip", "pmx_merge.hip",
+               "pmx_merge_from.hip",
                "pmx_moveifc.hip", "pmx_reach.hip", "pmx_part.hip"]
 HIPCC_FLAGS = [
     "-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared",

@@ -29,35 +29,20 @@
 // Orders come from indices and scans only: the atomics are min / max, whose
 // result does not depend on arrival order.  No kernel waits on another
 // workgroup.  Every index a kernel gathers through was range-checked by the
-// host while it packed the groups.
+// host while it packed the groups -- or, for a group that a context holds, by
+// pmx_merge_from.hip before it calls Merge::plan (pmx_merge.h: the plan and
+// the checks and packing the two front ends share).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <cstring>
 #include <vector>
 #include "pmx_device.h"
-#include "pmx_internal.h"
+#include "pmx_merge.h"
 
 namespace {
 
 const unsigned NONE = 0xffffffffu;
-
-// control words
-enum { MC_UNFILLED = 0, MC_TWICE = 1, MC_NCTL = 4 };
-// rows of the group table (ngrp + 1 entries each): points, tets, node
-// entries, face entries of the groups before g
-enum { GT_P = 0, GT_T = 1, GT_N = 2, GT_F = 3, GT_ROWS = 4 };
-
-// the last i with tab[i] <= x, tab ascending with tab[0] <= x (n entries)
-__device__ __forceinline__ int mg_find(const int *__restrict__ tab, int n, int x) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tab[mid] <= x) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 // seed[slot[i]] = the largest i < n
 __global__ __launch_bounds__(256) void k_mg_last(const int *__restrict__ slot, int64_t n, int *seed) {
@@ -279,45 +264,6 @@ __global__ __launch_bounds__(256) void k_mg_deinterleave(const double *__restric
 
 }  // namespace
 
-struct pmx_merge_plan {
-  int64_t P = 0, T = 0, NN = 0, NF = 0, NEN = 0, NEF = 0, np = 0, ne = 0, nnode = 0;
-  int ngrp = 0, next_node = 0;
-  SolDesc sd{};
-  std::vector<int> gt;                   // the group table, GT_ROWS x (ngrp + 1)
-  DevBuf<double> cxyz, csol, mxyz, msol, gs;
-  DevBuf<int4> ctet, mtet;
-  DevBuf<int> gtab, nep, nes, fet, fe1, fe2, extn, extf, eoff, nseed, fseed, crank, urank, hrank, turank, pmap,
-      psrc, pgrp, pold, tnew, tgrp, told, fval, em, epos, extn_new, on1, on2, of1, of2;
-  DevBuf<unsigned> firstent, creator, tfirst, ffirst, pfirst, ctl;
-  DevBuf<char> tmp;
-  DevEvent ev[2];
-  int row(int r, int g) const { return gt[(size_t)r * (ngrp + 1) + g]; }
-};
-
-namespace {
-
-struct Merge : pmx_call {
-  pmx_merge_plan *pl;
-  Merge(pmx_ctx *c, const char *w) : pmx_call{c, w, c->stream}, pl(c->merge) {}
-
-  template <class T> bool up(DevBuf<T> &d, const T *h, int64_t n, const char *what) {
-    return pmx_dgrow(ctx, d, (size_t)std::max<int64_t>(n, 1)) &&
-           (n == 0 || ok(hipMemcpyAsync(d.p, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice, s), what));
-  }
-  template <class T> bool fill(DevBuf<T> &d, int64_t n, int byte, const char *what) {
-    return pmx_dgrow(ctx, d, (size_t)std::max<int64_t>(n, 1)) &&
-           ok(hipMemsetAsync(d.p, byte, sizeof(T) * (size_t)std::max<int64_t>(n, 1), s), what);
-  }
-  template <class F> bool scan(F f, DevBuf<int> &out, int64_t n, const char *what) {
-    hipcub::CountingInputIterator<int> it(0);
-    hipcub::TransformInputIterator<int, F, hipcub::CountingInputIterator<int>> in(it, f);
-    return pmx_dgrow(ctx, out, (size_t)n + 1) && exclusive_sum(pl->tmp, in, out.p, n + 1, what);
-  }
-  bool word(int *dst, const int *src, const char *what) { return read_words(dst, src, 1, what); }
-
-  bool plan(int64_t nitemN, int64_t nitemF);
-};
-
 // the packed groups are on their way to the device; the rest happens there
 bool Merge::plan(int64_t nitemN, int64_t nitemF) {
   pmx_merge_plan &P = *pl;
@@ -402,12 +348,148 @@ bool Merge::plan(int64_t nitemN, int64_t nitemF) {
 }
 
 // a refused or failed plan leaves none behind
-int refuse(pmx_ctx *ctx) {
+int pmx_merge_refuse(pmx_ctx *ctx) {
   pmx_merge_free(ctx);
   return 0;
 }
 
-}  // namespace
+bool Merge::check_comm(int32_t ngrp, const void *groups, int nsol, const pmx_merge_comm *comm) {
+  if (ngrp < 1) return fail("ngrp < 1");
+  if (!groups) return fail("groups is NULL");
+  if (nsol < 0 || nsol > PMX_MAX_SOLS) return fail("nsol outside 0..PMX_MAX_SOLS");
+  const int64_t nitemN = comm ? comm->int_node_nitem : 0, nitemF = comm ? comm->int_face_nitem : 0;
+  const int next_n = comm ? comm->next_node : 0, next_f = comm ? comm->next_face : 0;
+  if (nitemN < 0 || nitemF < 0 || nitemN >= (1LL << 31) - 1 || nitemF >= (1LL << 31) - 1 || next_n < 0 || next_f < 0)
+    return fail("communicator sizes out of range");
+  if ((next_n > 0 && !comm->node_off) || (next_f > 0 && !comm->face_off)) return fail("a NULL view: external offsets");
+  return true;
+}
+
+bool Merge::check_host_group(const pmx_merge_group &G, int g, int nsol, bool first, SolDesc &sd) {
+  const std::string gs = " (group " + std::to_string(g) + ")";
+  if (G.np < 1 || G.ne < 1 || G.nnode < 0 || G.nface < 0) return fail("np, ne < 1 or a negative entry count" + gs);
+  if (!G.point_c || !G.tetra_v || G.point_stride < 24 || G.tetra_stride < 16 || (nsol > 0 && !G.sols) ||
+      (G.nnode > 0 && (!G.node_index1 || !G.node_index2)) || (G.nface > 0 && (!G.face_index1 || !G.face_index2)))
+    return fail("a NULL view or a stride too small" + gs);
+  int S = 0;
+  for (int i = 0; i < nsol; i++) {
+    const int sz = G.sols[i].size;
+    if (!G.sols[i].m) return fail("a NULL view: solution" + gs);
+    if (sz != 1 && sz != 3 && sz != 6) return fail("solution size must be 1, 3 or 6" + gs);
+    if (!first && sz != sd.size[i]) return fail("solution sizes differ between groups" + gs);
+    sd.size[i] = sz;
+    sd.off[i] = S;
+    S += sz;
+  }
+  sd.S = S;
+  return true;
+}
+
+bool Merge::check_ext(const pmx_merge_comm *comm, int64_t *pNEN, int64_t *pNEF) {
+  const int next_n = comm ? comm->next_node : 0, next_f = comm ? comm->next_face : 0;
+  const int64_t NEN = next_n > 0 ? comm->node_off[next_n] : 0, NEF = next_f > 0 ? comm->face_off[next_f] : 0;
+  if (NEN < 0 || NEF < 0 || NEN >= (1LL << 31) - 1 || NEF >= (1LL << 31) - 1 || (NEN > 0 && !comm->node_items) ||
+      (NEF > 0 && !comm->face_items))
+    return fail("external items: a NULL view or counts out of range");
+  for (int k = 0; k < next_n; k++)
+    if (comm->node_off[k] < 0 || comm->node_off[k] > comm->node_off[k + 1] || comm->node_off[0] != 0)
+      return fail("external node offsets not ascending from 0");
+  for (int k = 0; k < next_f; k++)
+    if (comm->face_off[k] < 0 || comm->face_off[k] > comm->face_off[k + 1] || comm->face_off[0] != 0)
+      return fail("external face offsets not ascending from 0");
+  *pNEN = NEN;
+  *pNEF = NEF;
+  return true;
+}
+
+bool Merge::pack_host_group(const pmx_merge_group &G, int g, int nsol, const SolDesc &sd, int64_t nitemN,
+                            int64_t nitemF, const MergeHostDst &d) {
+  const int S = sd.S;
+  const int64_t p0 = d.p0, t0 = d.t0;
+  const std::string gs = " (group " + std::to_string(g) + ")";
+  const char *pc = (const char *)G.point_c, *tc = (const char *)G.tetra_v;
+  int bad = 0;                           // 1 deleted tet, 2 vertex
+  pmx_par_for(1, G.np + 1, [&](int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; i++) {
+      const double *c = (const double *)(pc + i * G.point_stride);
+      double *x = d.x + 3 * (i - 1);
+      x[0] = c[0]; x[1] = c[1]; x[2] = c[2];
+      double *r = d.s + (int64_t)S * (i - 1);
+      for (int is = 0; is < nsol; is++) {
+        const int sz = sd.size[is];
+        const double *m = G.sols[is].m + i * sz;
+        for (int j = 0; j < sz; j++) r[sd.off[is] + j] = m[j];
+      }
+    }
+  });
+  pmx_par_for(1, G.ne + 1, [&](int64_t k0, int64_t k1) {
+    int b = 0;
+    for (int64_t k = k0; k < k1; k++) {
+      const int *v = (const int *)(tc + k * G.tetra_stride);
+      if (v[0] <= 0) { b |= 1; continue; }
+      int w[4];
+      for (int l = 0; l < 4; l++) {
+        if (v[l] < 1 || v[l] > G.np) { b |= 2; w[l] = (int)p0; }
+        else w[l] = (int)(p0 + v[l] - 1);
+      }
+      d.t[k - 1] = make_int4(w[0], w[1], w[2], w[3]);
+    }
+    if (b) __atomic_fetch_or(&bad, b, __ATOMIC_RELAXED);
+  });
+  if (bad & 1) return fail("a deleted tet (v[0] <= 0): the reference wants packed groups" + gs);
+  if (bad & 2) return fail("a vertex outside 1..np" + gs);
+  return pack_entries(G, g, G.np, G.ne, p0, t0, nitemN, nitemF, d);
+}
+
+bool Merge::pack_entries(const pmx_merge_group &G, int g, int64_t np, int64_t ne, int64_t p0, int64_t t0,
+                         int64_t nitemN, int64_t nitemF, const MergeHostDst &d) {
+  const std::string gs = " (group " + std::to_string(g) + ")";
+  int bad = 0;
+  pmx_par_for(0, G.nnode, [&](int64_t i0, int64_t i1) {
+    int b = 0;
+    for (int64_t i = i0; i < i1; i++) {
+      const int ip = G.node_index1[i], pos = G.node_index2[i];
+      if (ip < 1 || ip > np) { b |= 4; continue; }
+      if (pos < 0 || pos >= nitemN) { b |= 8; continue; }
+      d.np[i] = (int)(p0 + ip - 1);
+      d.ns[i] = pos;
+    }
+    if (b) __atomic_fetch_or(&bad, b, __ATOMIC_RELAXED);
+  });
+  pmx_par_for(0, G.nface, [&](int64_t j0, int64_t j1) {
+    int b = 0;
+    for (int64_t j = j0; j < j1; j++) {
+      const int v = G.face_index1[j], pos = G.face_index2[j];
+      if (v < 12 || (int64_t)v > 12 * ne + 11) { b |= 16; continue; }
+      if (pos < 0 || pos >= nitemF) { b |= 32; continue; }
+      d.ft[j] = (int)(t0 + v / 12 - 1);
+      d.f1[j] = v;
+      d.f2[j] = pos;
+    }
+    if (b) __atomic_fetch_or(&bad, b, __ATOMIC_RELAXED);
+  });
+  if (bad & 4) return fail("a node entry's point outside 1..np" + gs);
+  if (bad & 8) return fail("a node entry's position outside 0..int_node_nitem-1" + gs);
+  if (bad & 16) return fail("a face entry outside 12..12*ne+11" + gs);
+  if (bad & 32) return fail("a face entry's position outside 0..int_face_nitem-1" + gs);
+  return true;
+}
+
+bool Merge::pack_ext(const pmx_merge_comm *comm, int64_t nitemN, int64_t nitemF, int64_t NEN, int64_t NEF, int *hen,
+                     int *hef, int *heo) {
+  for (int64_t e = 0; e < NEN; e++) {
+    if (comm->node_items[e] < 0 || comm->node_items[e] >= nitemN) return fail("an external node item out of range");
+    hen[e] = comm->node_items[e];
+  }
+  for (int64_t e = 0; e < NEF; e++) {
+    if (comm->face_items[e] < 0 || comm->face_items[e] >= nitemF) return fail("an external face item out of range");
+    hef[e] = comm->face_items[e];
+  }
+  const int next_n = comm ? comm->next_node : 0;
+  heo[0] = 0;
+  for (int k = 0; k < next_n; k++) heo[k + 1] = (int)comm->node_off[k + 1];
+  return true;
+}
 
 void pmx_merge_free(pmx_ctx *ctx) {
   pmx_merge_plan *P = ctx->merge;      // its members release themselves
@@ -441,15 +523,11 @@ int pmx_merge_groups(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_group *groups, 
   ctx->merge = new pmx_merge_plan();
   Merge M{ctx, "pmx_merge_groups"};
   pmx_merge_plan &P = *ctx->merge;
-  auto no = [&](const std::string &what) { M.fail(what); return refuse(ctx); };
-  if (ngrp < 1) return no("ngrp < 1");
-  if (!groups) return no("groups is NULL");
-  if (nsol < 0 || nsol > PMX_MAX_SOLS) return no("nsol outside 0..PMX_MAX_SOLS");
+  auto refuse = [&]() { return pmx_merge_refuse(ctx); };
+  auto no = [&](const std::string &what) { M.fail(what); return refuse(); };
+  if (!M.check_comm(ngrp, groups, nsol, comm)) return refuse();
   const int64_t nitemN = comm ? comm->int_node_nitem : 0, nitemF = comm ? comm->int_face_nitem : 0;
-  const int next_n = comm ? comm->next_node : 0, next_f = comm ? comm->next_face : 0;
-  if (nitemN < 0 || nitemF < 0 || nitemN >= (1LL << 31) - 1 || nitemF >= (1LL << 31) - 1 || next_n < 0 || next_f < 0)
-    return no("communicator sizes out of range");
-  if ((next_n > 0 && !comm->node_off) || (next_f > 0 && !comm->face_off)) return no("a NULL view: external offsets");
+  const int next_n = comm ? comm->next_node : 0;
   // sizes and views
   const int G1 = ngrp + 1;
   std::vector<int64_t> off((size_t)GT_ROWS * G1, 0);
@@ -458,22 +536,7 @@ int pmx_merge_groups(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_group *groups, 
   sd.imet = -1;
   for (int g = 0; g < ngrp; g++) {
     const pmx_merge_group &G = groups[g];
-    const std::string gs = " (group " + std::to_string(g) + ")";
-    if (G.np < 1 || G.ne < 1 || G.nnode < 0 || G.nface < 0) return no("np, ne < 1 or a negative entry count" + gs);
-    if (!G.point_c || !G.tetra_v || G.point_stride < 24 || G.tetra_stride < 16 || (nsol > 0 && !G.sols) ||
-        (G.nnode > 0 && (!G.node_index1 || !G.node_index2)) || (G.nface > 0 && (!G.face_index1 || !G.face_index2)))
-      return no("a NULL view or a stride too small" + gs);
-    int S = 0;
-    for (int i = 0; i < nsol; i++) {
-      const int sz = G.sols[i].size;
-      if (!G.sols[i].m) return no("a NULL view: solution" + gs);
-      if (sz != 1 && sz != 3 && sz != 6) return no("solution size must be 1, 3 or 6" + gs);
-      if (g > 0 && sz != sd.size[i]) return no("solution sizes differ between groups" + gs);
-      sd.size[i] = sz;
-      sd.off[i] = S;
-      S += sz;
-    }
-    sd.S = S;
+    if (!M.check_host_group(G, g, nsol, g == 0, sd)) return refuse();
     off[GT_P * G1 + g + 1] = off[GT_P * G1 + g] + G.np;
     off[GT_T * G1 + g + 1] = off[GT_T * G1 + g] + G.ne;
     off[GT_N * G1 + g + 1] = off[GT_N * G1 + g] + G.nnode;
@@ -485,16 +548,8 @@ int pmx_merge_groups(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_group *groups, 
   }
   const int64_t NP = off[GT_P * G1 + ngrp], T = off[GT_T * G1 + ngrp], NN = off[GT_N * G1 + ngrp],
                 NF = off[GT_F * G1 + ngrp];
-  const int64_t NEN = next_n > 0 ? comm->node_off[next_n] : 0, NEF = next_f > 0 ? comm->face_off[next_f] : 0;
-  if (NEN < 0 || NEF < 0 || NEN >= (1LL << 31) - 1 || NEF >= (1LL << 31) - 1 || (NEN > 0 && !comm->node_items) ||
-      (NEF > 0 && !comm->face_items))
-    return no("external items: a NULL view or counts out of range");
-  for (int k = 0; k < next_n; k++)
-    if (comm->node_off[k] < 0 || comm->node_off[k] > comm->node_off[k + 1] || comm->node_off[0] != 0)
-      return no("external node offsets not ascending from 0");
-  for (int k = 0; k < next_f; k++)
-    if (comm->face_off[k] < 0 || comm->face_off[k] > comm->face_off[k + 1] || comm->face_off[0] != 0)
-      return no("external face offsets not ascending from 0");
+  int64_t NEN = 0, NEF = 0;
+  if (!M.check_ext(comm, &NEN, &NEF)) return refuse();
   P.ngrp = ngrp;
   P.next_node = next_n;
   P.sd = sd;
@@ -510,98 +565,31 @@ int pmx_merge_groups(pmx_ctx *ctx, int32_t ngrp, const pmx_merge_group *groups, 
                o_o = o_e + pmx_call::al256((size_t)(NEN + NEF) * 4), total = o_o + pmx_call::al256((size_t)(next_n + 1) * 4);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return no("sync");   // the arena may still feed an earlier copy
   char *stg = pmx_hstage(ctx, total);
-  if (!stg) return refuse(ctx);
+  if (!stg) return refuse();
   double *hx = (double *)(stg + o_x), *hs = (double *)(stg + o_s);
   int4 *ht = (int4 *)(stg + o_t);
   int *hnp = (int *)(stg + o_n), *hns = hnp + NN;
   int *hft = (int *)(stg + o_f), *hf1 = hft + NF, *hf2 = hf1 + NF;
   int *hen = (int *)(stg + o_e), *hef = hen + NEN, *heo = (int *)(stg + o_o);
-  int bad = 0;                           // 1 deleted tet, 2 vertex
   for (int g = 0; g < ngrp; g++) {
-    const pmx_merge_group &G = groups[g];
     const int64_t p0 = off[GT_P * G1 + g], t0 = off[GT_T * G1 + g], n0 = off[GT_N * G1 + g], f0 = off[GT_F * G1 + g];
-    const std::string gs = " (group " + std::to_string(g) + ")";
-    const char *pc = (const char *)G.point_c, *tc = (const char *)G.tetra_v;
-    pmx_par_for(1, G.np + 1, [&](int64_t i0, int64_t i1) {
-      for (int64_t i = i0; i < i1; i++) {
-        const double *c = (const double *)(pc + i * G.point_stride);
-        double *d = hx + 3 * (p0 + i - 1);
-        d[0] = c[0]; d[1] = c[1]; d[2] = c[2];
-        double *r = hs + (int64_t)S * (p0 + i - 1);
-        for (int is = 0; is < nsol; is++) {
-          const int sz = sd.size[is];
-          const double *m = G.sols[is].m + i * sz;
-          for (int j = 0; j < sz; j++) r[sd.off[is] + j] = m[j];
-        }
-      }
-    });
-    pmx_par_for(1, G.ne + 1, [&](int64_t k0, int64_t k1) {
-      int b = 0;
-      for (int64_t k = k0; k < k1; k++) {
-        const int *v = (const int *)(tc + k * G.tetra_stride);
-        if (v[0] <= 0) { b |= 1; continue; }
-        int w[4];
-        for (int l = 0; l < 4; l++) {
-          if (v[l] < 1 || v[l] > G.np) { b |= 2; w[l] = (int)p0; }
-          else w[l] = (int)(p0 + v[l] - 1);
-        }
-        ht[t0 + k - 1] = make_int4(w[0], w[1], w[2], w[3]);
-      }
-      if (b) __atomic_fetch_or(&bad, b, __ATOMIC_RELAXED);
-    });
-    if (bad & 1) return no("a deleted tet (v[0] <= 0): the reference wants packed groups" + gs);
-    if (bad & 2) return no("a vertex outside 1..np" + gs);
-    pmx_par_for(0, G.nnode, [&](int64_t i0, int64_t i1) {
-      int b = 0;
-      for (int64_t i = i0; i < i1; i++) {
-        const int ip = G.node_index1[i], pos = G.node_index2[i];
-        if (ip < 1 || ip > G.np) { b |= 4; continue; }
-        if (pos < 0 || pos >= nitemN) { b |= 8; continue; }
-        hnp[n0 + i] = (int)(p0 + ip - 1);
-        hns[n0 + i] = pos;
-      }
-      if (b) __atomic_fetch_or(&bad, b, __ATOMIC_RELAXED);
-    });
-    pmx_par_for(0, G.nface, [&](int64_t j0, int64_t j1) {
-      int b = 0;
-      for (int64_t j = j0; j < j1; j++) {
-        const int v = G.face_index1[j], pos = G.face_index2[j];
-        if (v < 12 || (int64_t)v > 12 * G.ne + 11) { b |= 16; continue; }
-        if (pos < 0 || pos >= nitemF) { b |= 32; continue; }
-        hft[f0 + j] = (int)(t0 + v / 12 - 1);
-        hf1[f0 + j] = v;
-        hf2[f0 + j] = pos;
-      }
-      if (b) __atomic_fetch_or(&bad, b, __ATOMIC_RELAXED);
-    });
-    if (bad & 4) return no("a node entry's point outside 1..np" + gs);
-    if (bad & 8) return no("a node entry's position outside 0..int_node_nitem-1" + gs);
-    if (bad & 16) return no("a face entry outside 12..12*ne+11" + gs);
-    if (bad & 32) return no("a face entry's position outside 0..int_face_nitem-1" + gs);
+    const MergeHostDst d{hx + 3 * p0, hs + (int64_t)S * p0, ht + t0, hnp + n0, hns + n0, hft + f0, hf1 + f0, hf2 + f0, p0, t0};
+    if (!M.pack_host_group(groups[g], g, nsol, sd, nitemN, nitemF, d)) return refuse();
   }
-  for (int64_t e = 0; e < NEN; e++) {
-    if (comm->node_items[e] < 0 || comm->node_items[e] >= nitemN) return no("an external node item out of range");
-    hen[e] = comm->node_items[e];
-  }
-  for (int64_t e = 0; e < NEF; e++) {
-    if (comm->face_items[e] < 0 || comm->face_items[e] >= nitemF) return no("an external face item out of range");
-    hef[e] = comm->face_items[e];
-  }
-  heo[0] = 0;
-  for (int k = 0; k < next_n; k++) heo[k + 1] = (int)comm->node_off[k + 1];
+  if (!M.pack_ext(comm, nitemN, nitemF, NEN, NEF, hen, hef, heo)) return refuse();
   // uploads, then the device
-  if (!pmx_create_events(P.ev) || !M.ok(hipEventRecord(P.ev[0], M.s), "event record")) return refuse(ctx);
+  if (!pmx_create_events(P.ev) || !M.ok(hipEventRecord(P.ev[0], M.s), "event record")) return refuse();
   if (!M.up(P.cxyz, (const double *)hx, 3 * NP, "points") || !M.up(P.csol, (const double *)hs, (int64_t)S * NP, "solutions") ||
       !M.up(P.ctet, (const int4 *)ht, T, "tets") || !M.up(P.nep, (const int *)hnp, NN, "node entries") ||
       !M.up(P.nes, (const int *)hns, NN, "node entries") || !M.up(P.fet, (const int *)hft, NF, "face entries") ||
       !M.up(P.fe1, (const int *)hf1, NF, "face entries") || !M.up(P.fe2, (const int *)hf2, NF, "face entries") ||
       !M.up(P.extn, (const int *)hen, NEN, "external items") || !M.up(P.extf, (const int *)hef, NEF, "external items") ||
       !M.up(P.eoff, (const int *)heo, next_n + 1, "external offsets"))
-    return refuse(ctx);
-  if (!M.plan(nitemN, nitemF)) return refuse(ctx);
-  if (!M.ok(hipEventRecord(P.ev[1], M.s), "event record") || !M.sync("plan")) return refuse(ctx);
+    return refuse();
+  if (!M.plan(nitemN, nitemF)) return refuse();
+  if (!M.ok(hipEventRecord(P.ev[1], M.s), "event record") || !M.sync("plan")) return refuse();
   float ms = 0.f;
-  if (!M.ok(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]), "event time")) return refuse(ctx);
+  if (!M.ok(hipEventElapsedTime(&ms, P.ev[0], P.ev[1]), "event time")) return refuse();
   // the inputs' device copies are not needed again
   P.cxyz.release();
   P.csol.release();
@@ -666,11 +654,14 @@ int pmx_merge_maps(pmx_ctx *ctx, int32_t g, int *point_new, int *tet_new) {
   if (!ctx->merge) { M.fail("no plan: call pmx_merge_groups"); return 0; }
   pmx_merge_plan &P = *ctx->merge;
   if (g < 0 || g >= P.ngrp) { M.fail("group out of range"); return 0; }
-  const int64_t p0 = P.row(GT_P, g), npg = P.row(GT_P, g + 1) - p0, t0 = P.row(GT_T, g), neg = P.row(GT_T, g + 1) - t0;
-  if (point_new &&
-      !M.ok(hipMemcpyAsync(point_new, P.pmap.p + p0, 4 * (size_t)npg, hipMemcpyDeviceToHost, M.s), "download"))
+  // a plan of pmx_merge_groups_from: the maps in the sources' own numbering
+  const bool own = !P.uoff.empty();
+  const int64_t p0 = own ? P.uoff[g] : P.row(GT_P, g), p1 = own ? P.uoff[g + 1] : P.row(GT_P, g + 1);
+  const int64_t t0 = own ? P.uoff[P.ngrp + 1 + g] : P.row(GT_T, g), t1 = own ? P.uoff[P.ngrp + 2 + g] : P.row(GT_T, g + 1);
+  const int *pm = own ? P.upmap.p : P.pmap.p, *tm = own ? P.utnew.p : P.tnew.p;
+  if (point_new && !M.ok(hipMemcpyAsync(point_new, pm + p0, 4 * (size_t)(p1 - p0), hipMemcpyDeviceToHost, M.s), "download"))
     return 0;
-  if (tet_new && !M.ok(hipMemcpyAsync(tet_new, P.tnew.p + t0, 4 * (size_t)neg, hipMemcpyDeviceToHost, M.s), "download"))
+  if (tet_new && !M.ok(hipMemcpyAsync(tet_new, tm + t0, 4 * (size_t)(t1 - t0), hipMemcpyDeviceToHost, M.s), "download"))
     return 0;
   return M.sync("maps") ? 1 : 0;
 }

@@ -21,7 +21,7 @@ Names and argument meaning follow the reference:
   another context's background on the device (``PMMG_update_oldGrps``,
   src/libparmmg1.c:653), :meth:`Transfer.download_surface` reads a
   background's boundary trias back.
-* :meth:`Transfer.merge_groups`, :meth:`Transfer.merge_fetch`,
+* :meth:`Transfer.merge_groups`, :meth:`Transfer.merge_groups_from`, :meth:`Transfer.merge_fetch`,
   :meth:`Transfer.merge_maps`, :meth:`Transfer.merge_adopt`,
   :meth:`Transfer.merge_release` -- ``PMMG_merge_grps``
   (src/mergemesh_pmmg.c), the merged group kept on the device.
@@ -726,26 +726,37 @@ class Transfer:
         keep = []
         i32 = lambda a: np.ascontiguousarray(a, np.int32)
         gv = (N.MergeGroup * max(ngrp, 1))()
-        nsol = len(groups[0]["sols"]) if ngrp else 0
+        held = lambda d: d.get("held")
+        nsol = (len(held(groups[0]).sizes) if held(groups[0]) is not None else len(groups[0]["sols"])) if ngrp else 0
+        sol_sizes = []
+        sizes = []
         for g, d in enumerate(groups):
-            tv, xyz = i32(d["tetra_v"]), np.ascontiguousarray(d["xyz"], np.float64)
-            sols = [np.ascontiguousarray(s, np.float64) for s in d["sols"]]
-            if len(sols) != nsol:
-                raise ValueError("the groups differ in their number of solutions")
-            views = (N.SolView * max(nsol, 1))()
-            for i, a in enumerate(sols):
-                views[i].size = a.shape[1] if a.ndim == 2 else 1
-                views[i].m = _dp(a)
             idx = {k: i32(d.get(k, np.zeros(0))) for k in ("node_index1", "node_index2", "face_index1", "face_index2")}
             if len(idx["node_index1"]) != len(idx["node_index2"]) or len(idx["face_index1"]) != len(idx["face_index2"]):
                 raise ValueError("index1 and index2 of a communicator differ in length")
-            keep += [tv, xyz, sols, views, idx]
             v = gv[g]
-            v.np, v.ne = xyz.shape[0] - 1, tv.shape[0] - 1
-            v.point_c, v.point_stride = _dp(xyz), 24
-            v.tetra_v, v.tetra_stride = _ip(tv), 16
-            v.sols = views
             v.nnode, v.nface = len(idx["node_index1"]), len(idx["face_index1"])
+            if held(d) is not None:
+                # the context's group: only the index arrays are read, in its own numbering
+                keep += [idx]
+                sizes.append((held(d).bg_np, held(d).bg_ne))
+                sol_sizes = sol_sizes if g else [int(s) for s in held(d).sizes]
+            else:
+                tv, xyz = i32(d["tetra_v"]), np.ascontiguousarray(d["xyz"], np.float64)
+                sols = [np.ascontiguousarray(s, np.float64) for s in d["sols"]]
+                if len(sols) != nsol:
+                    raise ValueError("the groups differ in their number of solutions")
+                views = (N.SolView * max(nsol, 1))()
+                for i, a in enumerate(sols):
+                    views[i].size = a.shape[1] if a.ndim == 2 else 1
+                    views[i].m = _dp(a)
+                keep += [tv, xyz, sols, views, idx]
+                v.np, v.ne = xyz.shape[0] - 1, tv.shape[0] - 1
+                v.point_c, v.point_stride = _dp(xyz), 24
+                v.tetra_v, v.tetra_stride = _ip(tv), 16
+                v.sols = views
+                sizes.append((int(v.np), int(v.ne)))
+                sol_sizes = sol_sizes if g else [int(w.size) for w in views[:nsol]]
             for k, a in idx.items():
                 setattr(v, k, _ip(a) if a.size else None)
         c = N.MergeComm()
@@ -761,9 +772,8 @@ class Transfer:
             setattr(c, "next_" + kind, len(lists))
             setattr(c, kind + "_off", off.ctypes.data_as(C.POINTER(N.i64)) if lists else None)
             setattr(c, kind + "_items", _ip(ext[kind][1]) if items.size else None)
-        meta = {"sol_sizes": [int(v.size) for v in keep[3][:nsol]] if ngrp else [],
-                "nen": len(ext["node"][1]), "nef": len(ext["face"][1]),
-                "np": [int(v.np) for v in gv[:ngrp]], "ne": [int(v.ne) for v in gv[:ngrp]]}
+        meta = {"sol_sizes": sol_sizes, "nen": len(ext["node"][1]), "nef": len(ext["face"][1]),
+                "np": [n for n, _ in sizes], "ne": [n for _, n in sizes]}
         return gv, nsol, c, meta, keep + [ext]
 
     def merge_groups(self, groups: list[dict], comm: dict | None = None) -> dict:
@@ -779,6 +789,29 @@ class Transfer:
         self._merge = None
         self._chk(self.lib.pmx_merge_groups(self.ctx, len(groups), gv, nsol, C.byref(c), C.byref(sz)),
                   "pmx_merge_groups")
+        sizes = np.array([sz.np, sz.ne, sz.nnode, sz.nface], np.int64)
+        self._merge = dict(meta, sizes=sizes)
+        return {"sizes": sizes}
+
+    def merge_groups_from(self, sources: list[dict], comm: dict | None = None) -> dict:
+        """merge_groups with sources that contexts hold (pmx_merge_groups_from).
+        A source is a dict as merge_groups takes it, or {"held": a Transfer on
+        this device, node_index1/2, face_index1/2}: the group that context
+        holds as its background, read on the device; its index arrays are in
+        that group's own numbering.  A held group may have unused points and
+        deleted tets: they are dropped, merge_maps(g) -- sized by the held
+        group's own np and ne -- holds 0 for them, and tet_old / point_old of
+        merge_fetch are ids in the held group's own numbering.  Returns sizes
+        as merge_groups does."""
+        gv, nsol, c, meta, keep = self._merge_views(sources, comm)
+        sv = (N.MergeSource * max(len(sources), 1))()
+        for g, d in enumerate(sources):
+            sv[g].held = d["held"].ctx if d.get("held") is not None else None
+            sv[g].g = gv[g]
+        sz = N.MergeSizes()
+        self._merge = None
+        self._chk(self.lib.pmx_merge_groups_from(self.ctx, len(sources), sv, nsol, C.byref(c), C.byref(sz)),
+                  "pmx_merge_groups_from")
         sizes = np.array([sz.np, sz.ne, sz.nnode, sz.nface], np.int64)
         self._merge = dict(meta, sizes=sizes)
         return {"sizes": sizes}
