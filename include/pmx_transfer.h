@@ -312,6 +312,25 @@ int pmx_pointmap_stats(pmx_ctx *ctx, int64_t atomics[2]);
 /* Inspection: copy the volume hint grid of the last run to host (cap cells);
  * returns the number of cells (0 on error). */
 int64_t pmx_debug_hint_grid(pmx_ctx *ctx, int *host, int64_t cap);
+/* Inspection: a hint grid as the last pmx_run built it and its walks read it:
+ * which = 0 the volume grid (cell -> a sampled tet whose centroid falls in
+ * it), 1 the tria grid (cell -> the largest tria whose centroid falls in it);
+ * 0 in an empty cell, cell (x, y, z) at x + dim[0] * (y + dim[1] * z).  desc
+ * (may be NULL): the descriptor the kernels used -- cells per axis, the
+ * fraction bits of the fixed-point vertex coordinates (volume grid only, 0
+ * for the tria grid), the bounding box minimum and dim / extent per axis.
+ * cells (NULL: the size query) receives every cell; cap: ints in cells.
+ * Returns the number of cells, or 0 + pmx_last_error: no step on the current
+ * background, more cells than cap, or the last step built no such grid (a
+ * PMX_RUN_POINTMAP step builds neither; a step without surface points, or
+ * with nothing to interpolate, no tria grid). */
+typedef struct {
+  int    dim[3];
+  int    qf[3];
+  double lo[3];
+  double inv[3];
+} pmx_grid_desc;
+int64_t pmx_debug_grid(pmx_ctx *ctx, int which, pmx_grid_desc *desc, int *cells, int64_t cap);
 /* Inspection: the process-wide number of live device and pinned allocations
  * the library owns (memory handed out by pmx_device_alloc is the caller's and
  * is not counted). */

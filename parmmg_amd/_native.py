@@ -83,6 +83,11 @@ class Group(C.Structure):
     ]
 
 
+class GridDesc(C.Structure):
+    """pmx_grid_desc: a hint grid's descriptor (pmx_debug_grid)."""
+    _fields_ = [("dim", C.c_int * 3), ("qf", C.c_int * 3), ("lo", C.c_double * 3), ("inv", C.c_double * 3)]
+
+
 class PointSources(C.Structure):
     """pmx_point_sources: one group's source vertices (MMG5_Point.src)."""
     _fields_ = [("src", iptr), ("stride", i64)]
@@ -254,6 +259,7 @@ SIGNATURES = {
     "pmx_device_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pmx_device_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pmx_debug_hint_grid": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "pmx_debug_grid": (C.c_int64, [C.c_void_p, C.c_int, C.POINTER(GridDesc), iptr, C.c_int64]),
     "pmx_debug_live_allocations": (C.c_int64, []),
     "pmx_build_adja": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
                                  C.c_void_p]),

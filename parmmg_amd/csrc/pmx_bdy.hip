@@ -805,6 +805,7 @@ bool pmx_ctx::launch_bdy(const VolArgs &a, hipStream_t s, bool pointmap) {
     if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(k_tria_hint_build, dim3((unsigned)std::max<int64_t>(nb, 1)), dim3(256), 0, s,
                        d_tris.p, d_xyz.p, nt, d_tgrid.p, tgd);
+    tgrid_built = true;
   }
   launch_bdy_walks(bdy_args(this, a, pointmap), d_ows.p, s, OVF_THREADS, false, pointmap);
   return C.hip(hipGetLastError(), "launch");

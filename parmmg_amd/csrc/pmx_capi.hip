@@ -304,6 +304,7 @@ struct Step : pmx_call {
 
 bool Step::begin() {
   ctx->ran = false;
+  ctx->vgrid_built = ctx->tgrid_built = false;
   ctx->eager_nch = 0;
   if (!ctx->have_bg || !ctx->have_pts) return fail("pmx_run: upload background and points first");
   hipSetDevice(ctx->device);
@@ -403,6 +404,7 @@ void Step::hint_build() {
                     packed && ctx->samples_sorted ? ctx->d_tets_sk.p : nullptr, ctx->d_tets.p, ctx->ne,
                     stride, ctx->d_grid.p, ctx->grid, ctx->d_xyzq.p, st,
                     packed && ctx->samples_owner ? ctx->nsamp : -1);
+  ctx->vgrid_built = true;
 }
 
 bool Step::classify_and_hint() {

@@ -284,6 +284,10 @@ struct pmx_ctx {
   DevBuf<int> d_tgrid;
   GridDesc tgd{};
   int64_t tcells = 0;
+  // the last step built the volume / the tria hint grid (pmx_debug_grid): a
+  // PMX_RUN_POINTMAP step builds neither, a step without surface points or
+  // with nothing to locate no tria grid
+  bool vgrid_built = false, tgrid_built = false;
 
   // group seams (pmx_groups.hip): constant-size metric of a step without a
   // background, and the frozen-point copy (buffers reused across calls)

@@ -320,6 +320,32 @@ int64_t pmx_debug_hint_grid(pmx_ctx *ctx, int *host, int64_t cap) {
   return ctx->gcells;
 }
 
+int64_t pmx_debug_grid(pmx_ctx *ctx, int which, pmx_grid_desc *desc, int *cells, int64_t cap) {
+  if (!ctx) return 0;
+  const pmx_call C{ctx, "pmx_debug_grid", ctx->stream};
+  if (which != 0 && which != 1) return C.fail("which is 0 (volume grid) or 1 (tria grid)"), 0;
+  if (!ctx->ran || !ctx->have_bg) return C.fail("no step has run on the current background"), 0;
+  if (!(which ? ctx->tgrid_built : ctx->vgrid_built))
+    return C.fail(which ? "the last step built no tria hint grid" : "the last step built no volume hint grid"), 0;
+  const GridDesc &g = which ? ctx->tgd : ctx->grid;
+  const int64_t n = which ? ctx->tcells : ctx->gcells;
+  if (desc)
+    for (int a = 0; a < 3; a++) {
+      desc->dim[a] = g.dim[a];
+      desc->qf[a] = which ? 0 : g.qf[a];     // the tria grid has no fixed-point coordinates
+      desc->lo[a] = g.lo[a];
+      desc->inv[a] = g.inv[a];
+    }
+  if (!cells) return n;                      // the size query
+  if (cap < n) return C.fail("more cells than cap"), 0;
+  (void)hipSetDevice(ctx->device);
+  if (!C.sync("stream") ||
+      !C.hip(hipMemcpy(cells, which ? ctx->d_tgrid.p : ctx->d_grid.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost),
+             "download"))
+    return 0;
+  return n;
+}
+
 int pmx_pointmap_stats(pmx_ctx *ctx, int64_t atomics[2]) {
   if (!ctx || !atomics) return 0;
   const pmx_call C{ctx};

@@ -298,6 +298,20 @@ class Transfer:
         self._chk(self.lib.pmx_download_starts(self.ctx, _ip(s), len(s)), "pmx_download_starts")
         return s
 
+    def debug_grid(self, which: int = 0) -> tuple[dict, np.ndarray]:
+        """The hint grid the last run built (pmx_debug_grid): which 0 the
+        volume grid, 1 the tria grid.  Returns ({"dim", "qf" (3,) int, "lo",
+        "inv" (3,) float64}, cells (dim[2], dim[1], dim[0]) int32).  Raises
+        when the last step built no such grid."""
+        d = N.GridDesc()
+        n = self.lib.pmx_debug_grid(self.ctx, which, C.byref(d), None, 0)
+        self._chk(n, "pmx_debug_grid")
+        cells = np.zeros(n, np.int32)
+        self._chk(self.lib.pmx_debug_grid(self.ctx, which, C.byref(d), _ip(cells), n), "pmx_debug_grid")
+        desc = {"dim": np.array(d.dim, np.int64), "qf": np.array(d.qf, np.int64),
+                "lo": np.array(d.lo, np.float64), "inv": np.array(d.inv, np.float64)}
+        return desc, cells.reshape(int(d.dim[2]), int(d.dim[1]), int(d.dim[0]))
+
     def border(self) -> tuple[np.ndarray, np.ndarray]:
         e = np.zeros(self.npts, np.int32)
         v = np.zeros(self.npts, np.int32)

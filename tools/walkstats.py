@@ -39,23 +39,22 @@ def main():
     h = np.bincount(np.clip(np.abs(steps), 0, 20))
     c = m.centroids()
     d = np.linalg.norm(c[st[vol] - 1] - x[vol], axis=1) * cfg["n"]
-    ng = cfg["n"] ** 3
-    grid = np.zeros(ng, np.int32)
-    tr.lib.pmx_debug_hint_grid(tr.ctx, grid.ctypes.data, ng)
-    # the cell of each sampled tet's centroid, recomputed on the host
-    ks = np.arange(1, m.ne + 1, 4)
-    cen = m.xyz[m.tet[ks]].mean(axis=1)
-    cell = np.clip((cen * cfg["n"]).astype(np.int64), 0, cfg["n"] - 1)
-    ci = cell[:, 0] + cfg["n"] * (cell[:, 1] + cfg["n"] * cell[:, 2])
-    ok = np.zeros(ng, bool)
-    gi = grid.astype(np.int64)
-    nz = gi > 0
-    # a cell's hint must be one of the samples whose centroid is in that cell
-    samp_cell = np.full(m.ne + 1, -1, np.int64)
-    samp_cell[ks] = ci
-    ok[nz] = samp_cell[gi[nz]] == np.nonzero(nz)[0]
-    out_grid = {"cells": ng, "empty": int((~nz).sum()), "wrong_cell": int((nz & ~ok).sum())}
-    del cen, cell, ci, samp_cell
+    # the grid the step built, held to the definitions of tests/start_ref.py
+    # with the descriptor the kernels used (any box, any dims)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import start_ref
+    desc, cells = tr.debug_grid(0)
+    order = 2 if os.environ.get("PMX_HINT_SAMPLE_ORDER") == "2" else 0
+    bad = start_ref.check_sizing(m, desc, cells.size, 0) + start_ref.check_volume_cells(m, desc, cells,
+                                                                                        args.hint_stride, order)
+    gi = cells.ravel().astype(np.int64)
+    nz = np.nonzero(gi > 0)[0]
+    ks = start_ref.sample(m, args.hint_stride, order)
+    home = np.full(m.ne + 2, -1, np.int64)
+    home[ks] = start_ref.cell_of(m, desc, ks)
+    wrong = int((home[np.minimum(gi[nz], m.ne + 1)] != nz).sum())
+    out_grid = {"dim": [int(v) for v in desc["dim"]], "cells": int(cells.size), "empty": int(cells.size - len(nz)),
+                "wrong_cell": wrong, "violations": bad}
     out = {"grid": out_grid, "config": args.config, "n": cfg["n"], "nvol": int(vol.sum()),
            "steps_hist": {int(i): int(v) for i, v in enumerate(h) if v},
            "steps_mean": float(np.abs(steps).mean()),
