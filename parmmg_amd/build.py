@@ -26,7 +26,7 @@ MESHGEN_SO = os.path.join(PKG, "libpmx_meshgen.so")
 ORACLE_SO = os.path.join(ORACLE, "liboracle.so")
 
 HIP_SOURCES = ["pmx_capi.hip", "pmx_points.hip", "pmx_results.hip", "pmx_hostpool.hip", "pmx_background.hip",
-               "pmx_kernels.hip", "pmx_walk.hip", "pmx_bdy.hip", "pmx_fans.hip", "pmx_seq.hip",
+               "pmx_starts.hip", "pmx_fallback.hip", "pmx_walk.hip", "pmx_bdy.hip", "pmx_fans.hip", "pmx_seq.hip",
                "pmx_quality.hip", "pmx_lengths.hip", "pmx_graph.hip", "pmx_reduce.hip", "pmx_groups.hip",
                "pmx_topo.hip", "pmx_medit.hip", "pmx_more.hip", "pmx_contig.hip", "pmx_split.hip", "pmx_merge.hip",
                "pmx_merge_from.hip",

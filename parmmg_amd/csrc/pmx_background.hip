@@ -1,4 +1,13 @@
-// pmx_background.hip -- how a mesh becomes the uploaded group (host only).
+// pmx_background.hip -- how a mesh becomes the uploaded group, host side and
+// kernels.
+//
+// k_build_tetrec     tet records (+ the every-4th-tet hint sample) from the
+//                    connectivity and its Mmg face adjacency
+// k_build_wrec       the walk's compact records from the tet records
+// k_promote,         a promotion: the step's points and results as vertex and
+// k_patch_rows       solution rows; the rows the step did not write
+// k_gather_rows      an adopted split group's rows, gathered by index
+// k_tri_records      Mmg-layout trias and adjt on the device -> tria records
 //
 // Three entry points install a background: pmx_upload_background (from the
 // host's Mmg arrays), pmx_promote_background (the last step's points and
@@ -16,6 +25,156 @@
 #include "pmx_transfer.h"
 #include "pmx_kernels.h"
 #include "pmx_internal.h"
+
+// ---- the kernels: records and rows of a background ---------------------------------
+
+// tet records from the new tets and their Mmg face adjacency
+// (adja[4*(k-1)+1+f] = 4*k'+f'), and the packed hint sample
+__global__ __launch_bounds__(256) void k_build_tetrec(const int4 *__restrict__ tv, const int *__restrict__ adja,
+                                                      int64_t ne, int stride, TetRec *__restrict__ tets,
+                                                      int4 *__restrict__ sample) {
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= ne;
+       k += (int64_t)gridDim.x * blockDim.x) {
+    TetRec r;
+    const int4 v = tv[k];
+    r.v[0] = v.x; r.v[1] = v.y; r.v[2] = v.z; r.v[3] = v.w;
+    for (int f = 0; f < 4; f++) r.nb[f] = k ? adja[4 * (k - 1) + 1 + f] / 4 : 0;
+    tets[k] = r;
+    if (k >= 1 && (k - 1) % stride == 0) sample[(k - 1) / stride] = v;
+  }
+}
+static void launch_build_tetrec(const int4 *tv, const int *adja, int64_t ne, int stride, TetRec *tets, int4 *sample,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(k_build_tetrec, dim3(pmx_grid(ne + 1, 16384)), dim3(256), 0, s, tv, adja, ne, stride, tets,
+                     sample);
+}
+
+// the walk's compact records (WRec, pmx_device.h) from the tet records, built
+// with them at every upload / promotion (a re-layout of the connectivity, like
+// the records themselves)
+__global__ __launch_bounds__(256) void k_build_wrec(const TetRec *__restrict__ tets, int64_t ne,
+                                                    WRec *__restrict__ wr, unsigned *__restrict__ nfar) {
+  unsigned cnt = 0;
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= ne;
+       k += (int64_t)gridDim.x * blockDim.x) {
+    WRec r;
+    wrec_encode(tets[k], k, r);
+    wr[k] = r;
+    const TetRec d = wrec_decode(r, tets, (int)k);
+    cnt += (d.nb[0] | d.nb[1] | d.nb[2] | d.nb[3]) < 0 ? 1u : 0u;
+  }
+  // tets with a far neighbour field, one atomic per wave
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(nfar, cnt);
+}
+// slots 0..ne; *h_nfar (pinned), when stream s gets there: the tets with a far
+// neighbour field (pmx_wrec.h); d_nfar one device word
+static void launch_build_wrec(const TetRec *tets, int64_t ne, WRec *wr, unsigned *d_nfar, unsigned *h_nfar,
+                              hipStream_t s) {
+  hipMemsetAsync(d_nfar, 0, sizeof(unsigned), s);
+  hipLaunchKernelGGL(k_build_wrec, dim3(pmx_grid(ne + 1, 16384)), dim3(256), 0, s, tets, ne, wr, d_nfar);
+  hipMemcpyAsync(h_nfar, d_nfar, sizeof(unsigned), hipMemcpyDeviceToHost, s);
+}
+
+// device residency across iterations (pmx_promote_background): the last
+// step's new points and results become the background: vertex ip (1..n) = new
+// point ip-1, its solution row = the step's output row ip-1
+__global__ __launch_bounds__(256) void k_promote(const double *__restrict__ q, const double *__restrict__ out,
+                                                 const uint16_t *__restrict__ qtag, int64_t n, int S,
+                                                 double *__restrict__ xyz, double *__restrict__ sol,
+                                                 uint16_t *__restrict__ ptag) {
+  for (int64_t ip = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ip <= n;
+       ip += (int64_t)gridDim.x * blockDim.x) {
+    if (ip == 0) {
+      xyz[0] = xyz[1] = xyz[2] = 0.0;
+      for (int j = 0; j < S; j++) sol[j] = 0.0;
+      if (ptag) ptag[0] = 0;
+      continue;
+    }
+    xyz[3 * ip] = q[3 * (ip - 1)];
+    xyz[3 * ip + 1] = q[3 * (ip - 1) + 1];
+    xyz[3 * ip + 2] = q[3 * (ip - 1) + 2];
+    for (int j = 0; j < S; j++) sol[ip * S + j] = out[(ip - 1) * S + j];
+    if (ptag) ptag[ip] = qtag[ip - 1];
+  }
+}
+static void launch_promote(const double *q, const double *out, const uint16_t *qtag, int64_t n, int S, double *xyz,
+                           double *sol, uint16_t *ptag, hipStream_t s) {
+  hipLaunchKernelGGL(k_promote, dim3(pmx_grid(n + 1, 16384)), dim3(256), 0, s, q, out, qtag, n, S, xyz, sol, ptag);
+}
+// rows the step did not write (not located, frozen, failed): the caller's
+// values, uploaded as (row, offset, size) + 6 doubles
+__global__ __launch_bounds__(256) void k_patch_rows(const int4 *__restrict__ ent, const double *__restrict__ vals,
+                                                    int64_t n, int S, double *__restrict__ sol) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int4 e = ent[i];                       // x: vertex, y: offset, z: size
+    for (int j = 0; j < e.z; j++) sol[(int64_t)e.x * S + e.y + j] = vals[6 * i + j];
+  }
+}
+void launch_patch_rows(const int4 *ent, const double *vals, int64_t n, int S, double *sol, hipStream_t s) {
+  if (n < 1) return;
+  hipLaunchKernelGGL(k_patch_rows, dim3(pmx_grid(n, 4096)), dim3(256), 0, s, ent, vals, n, S, sol);
+}
+
+// a split group as the background (pmx_split_adopt): xyz[i] / sol[i] = row
+// idx[i - 1] of sxyz / ssol for i = 1..n, row 0 zeroed (S = 0: sol is not touched).
+// One thread per 8-byte word of the destination, xyz's 3 (n + 1) words first,
+// then sol's S (n + 1): word t is stored at t, so a wave stores 512 contiguous
+// bytes, and the words of one source row are read by adjacent lanes.  idx is
+// a first-visit numbering: mostly ascending, so neighbouring rows share lines.
+__global__ __launch_bounds__(256) void k_gather_rows(const int *__restrict__ idx, int64_t n,
+                                                     const double *__restrict__ sxyz,
+                                                     const double *__restrict__ ssol, int S,
+                                                     double *__restrict__ xyz, double *__restrict__ sol) {
+  const int64_t nx = 3 * (n + 1), nw = nx + (int64_t)S * (n + 1);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nw; t += (int64_t)gridDim.x * blockDim.x) {
+    if (t < nx) {
+      const int64_t i = t / 3;
+      const int c = (int)(t - 3 * i);
+      xyz[t] = i ? sxyz[3 * (int64_t)idx[i - 1] + c] : 0.0;
+    } else {
+      const int64_t u = t - nx, i = u / S;
+      const int c = (int)(u - S * i);
+      sol[u] = i ? ssol[(int64_t)S * idx[i - 1] + c] : 0.0;
+    }
+  }
+}
+static void launch_gather_rows(const int *idx, int64_t n, const double *sxyz, const double *ssol, int S, double *xyz,
+                               double *sol, hipStream_t s) {
+  const int64_t nw = (int64_t)(3 + S) * (n + 1);
+  hipLaunchKernelGGL(k_gather_rows, dim3(pmx_grid(nw, 1 << 20)), dim3(256), 0, s, idx, n, sxyz, ssol, S, xyz, sol);
+}
+
+// Mmg-layout trias (3 (nt + 1) ints) and adjt (3 nt + 4 ints) on the device ->
+// TriRec records 0..nt, record 0 zeroed; an entry outside the range the host's
+// staging accepts (vertex 1..np, adjt >= 0, adjt / 3 <= nt) counts into *bad.
+// One thread per tria: its 3 vertices and 3 adjt entries in, one 32-B record
+// out (two 16-B stores, consecutive lanes consecutive records).  The ranges
+// are stage_trias'.
+__global__ __launch_bounds__(256) void k_tri_records(const int *__restrict__ tria, const int *__restrict__ adjt,
+                                                     int64_t nt, int64_t np, TriRec *__restrict__ tris,
+                                                     unsigned *__restrict__ bad) {
+  for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= nt;
+       k += (int64_t)gridDim.x * blockDim.x) {
+    int4 v = make_int4(0, 0, 0, 0), nb = make_int4(0, 0, 0, 0);
+    if (k) {
+      const int a0 = adjt[3 * (k - 1) + 1], a1 = adjt[3 * (k - 1) + 2], a2 = adjt[3 * (k - 1) + 3];
+      v = make_int4(tria[3 * k], tria[3 * k + 1], tria[3 * k + 2], 0);
+      nb = make_int4(a0 / 3, a1 / 3, a2 / 3, 0);
+      if (v.x < 1 || v.x > np || v.y < 1 || v.y > np || v.z < 1 || v.z > np || a0 < 0 || a1 < 0 || a2 < 0 ||
+          nb.x > nt || nb.y > nt || nb.z > nt)
+        atomicAdd(bad, 1u);
+    }
+    int4 *r = reinterpret_cast<int4 *>(tris + k);
+    r[0] = v;
+    r[1] = nb;
+  }
+}
+static void launch_tri_records(const int *tria, const int *adjt, int64_t nt, int64_t np, TriRec *tris, unsigned *bad,
+                               hipStream_t s) {
+  hipLaunchKernelGGL(k_tri_records, dim3(pmx_grid(nt + 1, 1 << 20)), dim3(256), 0, s, tria, adjt, nt, np, tris, bad);
+}
 
 namespace {
 

@@ -3,6 +3,10 @@
 // (pmx_run: the kernels of one transfer step sequenced on the context's
 // streams, in the phases of struct Step).
 //
+// k_prologue         the step's first launch: zeroes the write masks, the
+//                    counters and the volume hint grid
+// k_const_metric     the constant-size metric of every valid point
+//
 // The rest of the ABI's host side by subject: the new points and the new tets
 // are pmx_points.hip, the downloads and the statistics getters
 // pmx_results.hip, the host thread pool pmx_hostpool.hip.  How a mesh becomes
@@ -213,6 +217,61 @@ int pmx_device_upload(pmx_ctx *ctx, void *dev, const void *host, size_t bytes) {
 }  // extern "C"
 
 // ---- the step ---------------------------------------------------------------
+
+// the step's first launch zeroes up to PMX_ZERO_MAX device ranges
+#define PMX_ZERO_MAX 3
+struct ZeroRanges {
+  void *p[PMX_ZERO_MAX];
+  int64_t bytes[PMX_ZERO_MAX];
+  int n;
+  void add(void *ptr, int64_t b) {
+    if (ptr && b > 0) { p[n] = ptr; bytes[n] = b; n++; }
+  }
+};
+// the step's first launch: zero the ranges pmx_run adds -- the write masks,
+// the step's counters and the volume hint grid (the orphan marks come from
+// the host, the node -> trias counts are zeroed by their own builder)
+__global__ __launch_bounds__(256) void k_prologue(ZeroRanges z) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, st = (int64_t)gridDim.x * blockDim.x;
+  for (int r = 0; r < z.n; r++) {
+    // hipMalloc'd ranges: 256-B aligned starts
+    const int64_t n16 = z.bytes[r] / 16;
+    uint4 *q = reinterpret_cast<uint4 *>(z.p[r]);
+    for (int64_t i = t; i < n16; i += st) q[i] = make_uint4(0, 0, 0, 0);
+    char *c = reinterpret_cast<char *>(z.p[r]);
+    for (int64_t i = n16 * 16 + t; i < z.bytes[r]; i += st) c[i] = 0;
+  }
+}
+static void launch_prologue(const ZeroRanges &z, hipStream_t s) {
+  int64_t work = 1;
+  for (int r = 0; r < z.n; r++) work = std::max<int64_t>(work, z.bytes[r] / 16);
+  hipLaunchKernelGGL(k_prologue, dim3(pmx_grid(work, 4096)), dim3(256), 0, s, z);
+}
+
+// constant-size metric (MMG3D_Set_constantSize restated): all valid points
+__global__ __launch_bounds__(256) void k_const_metric(const int8_t *__restrict__ kind, int64_t nq,
+                                                      double *__restrict__ out, int S, int off,
+                                                      int size, double hsiz,
+                                                      uint8_t *__restrict__ wmask, int imet) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nq;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    if (kind[i] == KIND_NUL) continue;
+    double *o = out + i * S + off;
+    if (size == 1) {
+      o[0] = hsiz;
+    } else {
+      double v = 1.0 / (hsiz * hsiz);
+      o[0] = v; o[1] = 0.0; o[2] = 0.0; o[3] = v; o[4] = 0.0; o[5] = v;
+    }
+    wmask[i] |= (uint8_t)(1u << imet);
+  }
+}
+void launch_const_metric(const int8_t *kind, int64_t nq, double *out, int S, int off, int size,
+                         double hsiz, uint8_t *wmask, int imet, hipStream_t s) {
+  if (nq < 1) return;
+  hipLaunchKernelGGL(k_const_metric, dim3(pmx_grid(nq, 8192)), dim3(256), 0, s, kind, nq, out, S, off,
+                     size, hsiz, wmask, imet);
+}
 
 static void fill_vol_args(pmx_ctx *ctx, const SolDesc &sd, const pmx_run_opts &opts, VolArgs &A) {
   A.xyz = ctx->d_xyz.p; A.tets = ctx->d_tets.p; A.wrec = ctx->d_wrec.p; A.sol = ctx->d_sol.p; A.sd = sd;

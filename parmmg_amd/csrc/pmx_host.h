@@ -107,6 +107,12 @@ template <class T> inline bool pmx_dgrow(pmx_ctx *ctx, DevBuf<T> &b, size_t n) {
   return e == hipSuccess;
 }
 
+// workgroups of a grid-stride launch over `items` work items, `per` of them
+// per workgroup: min(max(ceil(items / per), 1), cap)
+inline unsigned pmx_grid(int64_t items, int64_t cap, int64_t per = 256) {
+  return (unsigned)std::min<int64_t>(std::max<int64_t>((items + per - 1) / per, 1), cap);
+}
+
 // One API call's view of its context: who reports, on which stream.
 struct pmx_call {
   pmx_ctx *ctx;

@@ -1,4 +1,5 @@
-// pmx_kernels.h -- kernel argument blocks and launchers (host <-> device).
+// pmx_kernels.h -- the argument blocks the kernels share and the launchers
+// called across source files (host <-> device), by defining source.
 #pragma once
 #include "pmx_device.h"
 
@@ -113,84 +114,30 @@ struct ExhArgs {
   long spin_limit;              // grid-barrier poll budget (debug: 0 forces a timeout)
 };
 
-// volume hint grid from every stride-th tet: `packed` = the host-packed
-// connectivity of tets 1, 1+stride, ... (stride == PMX_HINT_STRIDE), else the
-// tet records are read strided
-void launch_hint_build(const int4 *packed, const int *kidx, const TetRec *tets, int64_t ne, int stride, int *grid,
-                       GridDesc g, const unsigned long long *xyzq, hipStream_t s, int64_t nsamp = -1);
+// ---- pmx_capi.hip ------------------------------------------------------------------
+
+// constant-size metric (MMG3D_Set_constantSize restated): all valid points
+void launch_const_metric(const int8_t *kind, int64_t nq, double *out, int S, int off, int size,
+                         double hsiz, uint8_t *wmask, int imet, hipStream_t s);
+
+// ---- pmx_background.hip ------------------------------------------------------------
+
+// rows the step did not write: the caller's values, n entries (row, offset,
+// size) + 6 doubles each, into the rows of S doubles at sol
+void launch_patch_rows(const int4 *ent, const double *vals, int64_t n, int S, double *sol, hipStream_t s);
+
+// ---- pmx_starts.hip ----------------------------------------------------------------
+
 // per-background derived data: fixed-point grid coordinates of the vertices
 // (hint centroids) and the unit normals of the boundary trias
 // (PMMG_precompute_triaNormals, src/locate_pmmg.c:68-90), one launch
 void launch_bg_derive(const double *xyz, int64_t np, GridDesc g, unsigned long long *xyzq,
                       const TriRec *tris, int64_t nt, Pt4 *trn, hipStream_t s);
-// pointmap: the PM instantiations (a.grid holds the start elements)
-void launch_walk(const VolArgs &a, hipStream_t s, bool pointmap = false);
-void launch_exhaustive(const ExhArgs &e, const VolArgs &v, int blocks, hipStream_t s);
-void launch_const_metric(const int8_t *kind, int64_t nq, double *out, int S, int off, int size,
-                         double hsiz, uint8_t *wmask, int imet, hipStream_t s);
-// the step's first launch zeroes up to PMX_ZERO_MAX device ranges
-#define PMX_ZERO_MAX 3
-struct ZeroRanges {
-  void *p[PMX_ZERO_MAX];
-  int64_t bytes[PMX_ZERO_MAX];
-  int n;
-  void add(void *ptr, int64_t b) {
-    if (ptr && b > 0) { p[n] = ptr; bytes[n] = b; n++; }
-  }
-};
-void launch_prologue(const ZeroRanges &z, hipStream_t s);
-void launch_tet_conn(const TetRec *src, int64_t n, int4 *dst, hipStream_t s);
-// device residency (pmx_promote_background): new points + results -> background
-void launch_promote(const double *qxyz, const double *out, const uint16_t *qtag, int64_t n, int S, double *xyz,
-                    double *sol, uint16_t *ptag, hipStream_t s);
-// points in no valid new tet (mk == 0) after a step: rows back to untouched
-void launch_mark_new_tets(const int4 *tv, int64_t ne, uint8_t *mk, int64_t nmk, hipStream_t s);
-struct OrphanRows {
-  uint8_t *wmask;
-  int *elem, *status, *steps, *start, *edge, *vertex;
-  int8_t *kind;
-};
-void launch_orphans(const uint8_t *mk, int64_t n, uint8_t keep, const OrphanRows &r, hipStream_t s);
-void launch_patch_rows(const int4 *ent, const double *vals, int64_t n, int S, double *sol, hipStream_t s);
-// a split group as the background (pmx_split_adopt): xyz[i] / sol[i] = row
-// idx[i - 1] of sxyz / ssol for i = 1..n, row 0 zeroed (S = 0: sol is not touched)
-void launch_gather_rows(const int *idx, int64_t n, const double *sxyz, const double *ssol, int S, double *xyz,
-                        double *sol, hipStream_t s);
-// Mmg-layout trias (3 (nt + 1) ints) and adjt (3 nt + 4 ints) on the device ->
-// TriRec records 0..nt, record 0 zeroed; an entry outside the range the host's
-// staging accepts (vertex 1..np, adjt >= 0, adjt / 3 <= nt) counts into *bad
-void launch_tri_records(const int *tria, const int *adjt, int64_t nt, int64_t np, TriRec *tris, unsigned *bad,
-                        hipStream_t s);
-// new points, every step (the tag dispatch of the reference's vertex loop,
-// src/interpmesh_pmmg.c:541-560): kinds (mark != NULL: the orphan marks of
-// the new tets, 0 = in no valid new tet) and the order-preserving compaction into
-// the volume / surface lists; counts into nsel[0..1].  tcnt: scratch of cls_tiles(n) int2.
-#define CLS_TILE 16384               // 4 rounds of 256 threads x 16 points
-inline int64_t cls_tiles(int64_t n) { return (n + CLS_TILE - 1) / CLS_TILE; }
-void launch_classify(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind, int *vlist,
-                     int *blist, int *nsel, hipStream_t s);
-// PMX_RUN_POINTMAP.  The first-incident-element maps of a background
-// (PMMG_locate_setStart, src/locate_pmmg.c:931-986, whose loops keep the
-// first index that reaches a vertex): map[p] = the smallest valid tet
-// (v[0] > 0) holding vertex p, map[np + 1 + p] = the smallest tria, 0xffffffff
-// when none; 2 (np + 1) words, filled here.  cnt[0..1]: atomics issued.
-void launch_pmap_build(const TetRec *tets, int64_t ne, const TriRec *tris, int64_t nt, int64_t np,
-                       unsigned *map, unsigned *cnt, hipStream_t s);
-// launch_classify that also carries the source vertices src[0..n) through the
-// compaction: vstart[j] / bstart[j] = the start element of the j-th volume /
-// surface point, vmap / tmap of its source, 1 when the source is outside
-// 1..np or no element holds it
-struct PointMapArgs {
-  const int *src;
-  const unsigned *vmap, *tmap;
-  int64_t np;
-  int *vstart, *bstart;
-};
-void launch_classify_pointmap(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind,
-                              int *vlist, int *blist, int *nsel, const PointMapArgs &pm, hipStream_t s);
-
-void launch_build_tetrec(const int4 *tv, const int *adja, int64_t ne, int stride, TetRec *tets, int4 *sample,
-                         hipStream_t s);
+// volume hint grid from every stride-th tet: `packed` = the host-packed
+// connectivity of tets 1, 1+stride, ... (stride == PMX_HINT_STRIDE), else the
+// tet records are read strided
+void launch_hint_build(const int4 *packed, const int *kidx, const TetRec *tets, int64_t ne, int stride, int *grid,
+                       GridDesc g, const unsigned long long *xyzq, hipStream_t s, int64_t nsamp = -1);
 // the vertex-owner sample (k_vmin_owner): out[i] / kidx[i] the i-th vertex's
 // owner tet in vertex order; owner np + 1 words, flag and pos np + 1 ints each,
 // tmp owner_scan_temp_bytes(np) bytes; the sample count into *h_count (pinned)
@@ -198,12 +145,28 @@ size_t owner_scan_temp_bytes(int64_t np);
 bool launch_owner_sample(const TetRec *tets, int64_t ne, int64_t np, unsigned *owner, int *flag, int *pos,
                          int4 *out, int *kidx, unsigned *d_count, unsigned *h_count, void *tmp, size_t tmp_bytes,
                          hipStream_t s);
-// the walk's compact records from the tet records (slots 0..ne)
-// (*h_nfar, pinned, when stream s gets there: the tets with a far neighbour
-// field, pmx_wrec.h; d_nfar one device word)
-void launch_build_wrec(const TetRec *tets, int64_t ne, WRec *wr, unsigned *d_nfar, unsigned *h_nfar,
-                       hipStream_t s);
-// PMX_RUN_SEQUENTIAL_VOLUME (pmx_walk.hip): the volume sequence (point
+// PMX_RUN_POINTMAP.  The first-incident-element maps of a background
+// (PMMG_locate_setStart, src/locate_pmmg.c:931-986, whose loops keep the
+// first index that reaches a vertex): map[p] = the smallest valid tet
+// (v[0] > 0) holding vertex p, map[np + 1 + p] = the smallest tria, 0xffffffff
+// when none; 2 (np + 1) words, filled here.  cnt[0..1]: atomics issued.
+void launch_pmap_build(const TetRec *tets, int64_t ne, const TriRec *tris, int64_t nt, int64_t np,
+                       unsigned *map, unsigned *cnt, hipStream_t s);
+
+// ---- pmx_fallback.hip --------------------------------------------------------------
+
+// the near-face ties (k_ties), then the exhaustive scan of the stuck points
+// (k_fallback) on `blocks` co-resident workgroups
+void launch_exhaustive(const ExhArgs &e, const VolArgs &v, int blocks, hipStream_t s);
+// workgroups of k_fallback that can be co-resident with `share` other
+// launches of it on this device (0 on error)
+int fallback_coresident_blocks(int device, int share);
+
+// ---- pmx_walk.hip ------------------------------------------------------------------
+
+// the volume walk; pointmap: the PM instantiations (a.grid holds the start elements)
+void launch_walk(const VolArgs &a, hipStream_t s, bool pointmap = false);
+// PMX_RUN_SEQUENTIAL_VOLUME: the volume sequence (point
 // indices in the reference's visit order, its length on the device), each
 // point's speculative start and mesh->base, the speculation's "sure" flags,
 // the replay's tet flags (ne + 1, base compare), its control words and
@@ -226,7 +189,10 @@ void launch_seqv_resolve(const VolArgs &a, const SeqVolArgs &s, hipStream_t st);
 // flags[j] (j < nmax) = position j of the volume sequence must be checked by
 // the replay: not sure, or its start is not its predecessor's speculative tet
 void launch_seqv_flags(const VolArgs &a, const SeqVolArgs &s, int64_t nmax, uint8_t *flags, hipStream_t st);
-// The surface walks (pmx_bdy.hip): k_locate_bdy, its private-list overflow
+
+// ---- pmx_bdy.hip -------------------------------------------------------------------
+
+// The surface walks: k_locate_bdy, its private-list overflow
 // pass on ovf_threads threads -- linear lists in ows (OVF_THREADS threads'
 // worth, the step's) or, hashed, tables of GHS_WS_INTS zeroed ints per thread
 // (the sequential mode's speculative pass, whose walks from the predecessors'
@@ -238,7 +204,7 @@ void launch_bdy_walks(const BdyArgs &B, int *ows, hipStream_t s, int ovf_threads
                       bool pointmap = false);
 // k_exh_bdy on `blocks` workgroups, one stuck point each at a time
 void launch_exh_bdy(const BdyArgs &B, int blocks, hipStream_t s);
-// PMX_RUN_SEQUENTIAL_SURFACE's replay (k_seq_resolve, pmx_bdy.hip): the
+// PMX_RUN_SEQUENTIAL_SURFACE's replay (k_seq_resolve): the
 // surface sequence and its length on the device, each point's speculative
 // start, mesh->base and wedge flag, the reference's tria flags (nt + 1, base
 // compare) and point flags (np + 1, PF_INIT: still the incident-tria count
@@ -257,9 +223,8 @@ struct SeqBdyArgs {
   const int *cand, *ncand;   // the positions the replay must look at (sorted)
 };
 void launch_seq_resolve(const BdyArgs &B, const SeqBdyArgs &q, hipStream_t s);
-// workgroups of k_fallback that can be co-resident with `share` other
-// launches of it on this device (0 on error)
-int fallback_coresident_blocks(int device, int share);
+
+// ---- pmx_quality.hip, pmx_lengths.hip, pmx_graph.hip (stat_args) -------------------
 
 struct StatArgs {
   // vertex v at xyz[xstride * (v - vbase)] (background: dense xyz, stride 3,

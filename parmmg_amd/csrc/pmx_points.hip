@@ -1,9 +1,16 @@
-// pmx_points.hip -- the new points and the new tets (host side).
+// pmx_points.hip -- the new points and the new tets, host side and kernels.
 //
 // pmx_upload_points / pmx_upload_point_sources, the points' classification,
 // and NewTets: the new mesh's tets on the device with the orphan reset that
 // depends on them.  Every assignment to a NewTets member is in this file; its
 // states and transitions are the table at the struct (pmx_internal.h).
+//
+// k_mark_new_tets,   the orphan marks: the points some valid new tet holds
+// k_mark_new_tets_win  (plain byte stores / deduplicated in an LDS window)
+// k_orphans          the rows of the unmarked points back to "never visited"
+// k_cls_count,       the points' kinds and their order-preserving compaction
+// k_cls_write        into the volume / surface lists (PM: with the start
+//                    elements of a PMX_RUN_POINTMAP step)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
@@ -16,6 +23,163 @@
 #include "pmx_internal.h"
 
 // ---- the new tets ---------------------------------------------------------------
+
+// the orphan marks from the new tets on the device: point j (0-based) is
+// marked when a valid new tet (1-based vertex j + 1) holds it -- the
+// reference's vertex loop over the new tets (src/interpmesh_pmmg.c:535-541).
+// HBM-bound on the 16-B tet reads; the byte stores are what costs beyond
+// them (r06: 0.50 ms at C3 with four stores per tet), so a lane skips the
+// vertices its left neighbour -- the previous tet, which in any coherent
+// numbering shares most of them -- also holds (that lane stores them), and
+// each lane takes two tets per round (two loads in flight).
+// H tets per thread and iteration (loads in flight)
+template <int H>
+__global__ __launch_bounds__(256) void k_mark_new_tets(const int4 *__restrict__ tv, int64_t ne,
+                                                       uint8_t *__restrict__ mk) {
+  // (r06: an XCD-aware split -- each XCD one contiguous eighth of the tets,
+  // so its byte stores stay in its own L2 -- measured 0.565 vs 0.549 ms
+  // beside the step's prefix: not kept)
+  const int64_t st = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nit = (ne + H * st - 1) / (H * st);    // uniform trip count (the shuffles below)
+  const bool lane0 = (threadIdx.x & 63) == 0;
+  for (int64_t it = 0; it < nit; it++) {
+    const int64_t k0 = 1 + H * (it * st + (int64_t)blockIdx.x * blockDim.x) + threadIdx.x;
+    int4 v[H];
+#pragma unroll
+    for (int h = 0; h < H; h++) {
+      const int64_t k = k0 + h * blockDim.x;
+      v[h] = k <= ne ? tv[k] : make_int4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int h = 0; h < H; h++) {
+      const int4 a = v[h];
+      int4 u;
+      u.x = __shfl_up(a.x, 1, 64); u.y = __shfl_up(a.y, 1, 64);
+      u.z = __shfl_up(a.z, 1, 64); u.w = __shfl_up(a.w, 1, 64);
+      if (lane0 || u.x <= 0) u = make_int4(0, 0, 0, 0);   // no valid left neighbour: store all
+      if (a.x <= 0) continue;                             // !MG_EOK
+      const int w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int l = 0; l < 4; l++) {
+        const int q = w[l];
+        if (q != u.x && q != u.y && q != u.z && q != u.w) mk[q - 1] = 1;
+      }
+    }
+  }
+}
+// r06 (late): the marks deduplicated in LDS.  What bounds k_mark_new_tets is
+// not its 16-B tet stream but its byte stores: one L2 write request per lane
+// and vertex (≈ 1.5-2 per tet after the left-neighbour filter, a vertex is in
+// ≈ 24 tets).  Here a workgroup takes 256 H consecutive tets at a time and
+// marks their vertices in an LDS byte window [wb, wb + MW_WIN) anchored at
+// the chunk's first valid tet (a coherent numbering -- Morton or Scotch --
+// keeps a chunk's vertices together); the window is flushed as 32-bit words,
+// one global atomicOr per word that holds a mark (the bytes of the marks
+// array ORed: marks are only ever set, so concurrent chunks and the plain
+// byte stores of out-of-window vertices compose).  Any numbering stays
+// correct: a vertex outside the window is stored directly, as before.
+#define MW_WIN 16384
+template <int H>
+__global__ __launch_bounds__(256) void k_mark_new_tets_win(const int4 *__restrict__ tv, int64_t ne,
+                                                           uint8_t *__restrict__ mk, int64_t nmk) {
+  __shared__ unsigned win[MW_WIN / 4];
+  __shared__ int s_base;
+  unsigned *mk32 = reinterpret_cast<unsigned *>(mk);
+  uint8_t *wb8 = reinterpret_cast<uint8_t *>(win);
+  for (int i = threadIdx.x; i < MW_WIN / 4; i += 256) win[i] = 0u;
+  const int64_t C = 256 * H;
+  const int64_t nch = (ne + C - 1) / C;
+  const bool lane0 = (threadIdx.x & 63) == 0;
+  for (int64_t c = blockIdx.x; c < nch; c += gridDim.x) {        // uniform over the workgroup
+    const int64_t k0 = 1 + c * C + threadIdx.x;
+    int4 v[H];
+#pragma unroll
+    for (int h = 0; h < H; h++) {
+      const int64_t k = k0 + h * 256;
+      v[h] = k <= ne ? tv[k] : make_int4(0, 0, 0, 0);
+    }
+    // window anchor: the first valid tet's smallest vertex, less a quarter
+    // window (vertices of a chunk's later cells may precede it), 4-aligned
+    if (threadIdx.x == 0) {
+      const int4 a = v[0];
+      const int m = a.x > 0 ? min(min(a.x, a.y), min(a.z, a.w)) - 1 : 0;
+      s_base = max(0, m - MW_WIN / 4) & ~3;
+    }
+    __syncthreads();
+    const int wb = s_base;
+#pragma unroll
+    for (int h = 0; h < H; h++) {
+      const int4 a = v[h];
+      int4 u;
+      u.x = __shfl_up(a.x, 1, 64); u.y = __shfl_up(a.y, 1, 64);
+      u.z = __shfl_up(a.z, 1, 64); u.w = __shfl_up(a.w, 1, 64);
+      if (lane0 || u.x <= 0) u = make_int4(0, 0, 0, 0);
+      if (a.x <= 0) continue;                             // !MG_EOK
+      const int w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int l = 0; l < 4; l++) {
+        const int q = w[l];
+        if (q == u.x || q == u.y || q == u.z || q == u.w) continue;
+        const unsigned off = (unsigned)(q - 1 - wb);
+        if (off < (unsigned)MW_WIN) wb8[off] = 1;
+        else mk[q - 1] = 1;
+      }
+    }
+    __syncthreads();
+    // flush: one atomicOr per word holding a mark, then clear it
+    const int64_t w0 = wb >> 2;
+    for (int i = threadIdx.x; i < MW_WIN / 4; i += 256) {
+      const unsigned x = win[i];
+      if (x) {
+        if (w0 + i < (nmk + 3) / 4) atomicOr(mk32 + w0 + i, x);
+        win[i] = 0u;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// the window kernel when the sizes allow (its word flush indexes in 32 bits),
+// else the plain marks
+static void launch_mark_new_tets(const int4 *tv, int64_t ne, uint8_t *mk, int64_t nmk, hipStream_t s) {
+  if (ne < 1) return;
+  if (nmk > 0 && nmk < INT32_MAX - MW_WIN) {
+    hipLaunchKernelGGL(k_mark_new_tets_win<4>, dim3(pmx_grid(ne, 4096, 256 * 4)), dim3(256), 0, s, tv, ne, mk, nmk);
+    return;
+  }
+  hipLaunchKernelGGL(k_mark_new_tets<2>, dim3(pmx_grid(ne, 8192, 256 * 2)), dim3(256), 0, s, tv, ne, mk);
+}
+
+// the rows of points in no valid new tet, after a step that located them:
+// back to untouched (the constant-size bit kept), element / status / steps /
+// start 0, edge / vertex unset (-1), and their kind KIND_ORPH, so that the
+// locate statistics count only the points the reference visits (a NUL or
+// frozen point keeps its kind: the step never located it)
+struct OrphanRows {
+  uint8_t *wmask;
+  int *elem, *status, *steps, *start, *edge, *vertex;
+  int8_t *kind;
+};
+__global__ __launch_bounds__(256) void k_orphans(const uint8_t *__restrict__ mk, int64_t n, uint8_t keep,
+                                                 OrphanRows r) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+    if (mk[j]) continue;
+    r.wmask[j] &= keep;
+    r.elem[j] = 0;
+    r.status[j] = 0;
+    r.steps[j] = 0;
+    r.start[j] = 0;
+    r.edge[j] = -1;
+    r.vertex[j] = -1;
+    const int8_t k = r.kind[j];
+    if (k == KIND_VOL || k == KIND_BDY) r.kind[j] = KIND_ORPH;
+  }
+}
+// points in no valid new tet (mk == 0) after a step: rows back to untouched
+static void launch_orphans(const uint8_t *mk, int64_t n, uint8_t keep, const OrphanRows &r, hipStream_t s) {
+  if (n < 1) return;
+  hipLaunchKernelGGL(k_orphans, dim3(pmx_grid(n, 4096)), dim3(256), 0, s, mk, n, keep, r);
+}
 
 // One row of the caller's new tets (vertices are view indices first ..
 // first + n - 1) as the packed record, vertex = view index - first + 1; a
@@ -252,6 +416,220 @@ bool NewTets::replace(const int *tetra_v, int64_t tetra_stride, int64_t ne) {
   n = ne;
   have = true;
   return true;
+}
+
+// ---- new points: classification on the device (pmx_upload_points) ---------------
+
+// new points, every step (the tag dispatch of the reference's vertex loop,
+// src/interpmesh_pmmg.c:541-560): kinds (mark != NULL: the orphan marks of
+// the new tets, 0 = in no valid new tet) and the order-preserving compaction into
+// the volume / surface lists; counts into nsel[0..1].  tcnt: scratch of cls_tiles(n) int2.
+#define CLS_TILE 16384               // 4 rounds of 256 threads x 16 points
+static inline int64_t cls_tiles(int64_t n) { return (n + CLS_TILE - 1) / CLS_TILE; }
+
+// sum over the 256-thread block, in every thread (red: 4 LDS slots)
+__device__ __forceinline__ int2 block_sum2(int2 v, int2 *red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    v.x += __shfl_xor(v.x, o, 64);
+    v.y += __shfl_xor(v.y, o, 64);
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int2 r = red[0];
+#pragma unroll
+  for (int w = 1; w < 4; w++) { r.x += red[w].x; r.y += red[w].y; }
+  return r;
+}
+
+// The kinds of the 16 points j0 .. j0+15 of one thread (j0 % 16 == 0): two
+// 16-B tag loads and one 16-B mark load instead of 16 narrow loads per lane
+// (r03: the one-point-per-lane rounds were latency-bound, 0.12 ms at C3 for
+// 17 M points); points at or past n get 0xff.  kw: the kinds, 4 per word.
+__device__ __forceinline__ void kinds16(const uint16_t *__restrict__ tag, const uint8_t *__restrict__ mark,
+                                        int64_t j0, int64_t n, unsigned kw[4], int &cv, int &cb) {
+  unsigned tw[8], mw[4];
+  if (j0 + 16 <= n) {
+    if (tag) {
+      const uint4 a = reinterpret_cast<const uint4 *>(tag + j0)[0];
+      const uint4 b = reinterpret_cast<const uint4 *>(tag + j0)[1];
+      tw[0] = a.x; tw[1] = a.y; tw[2] = a.z; tw[3] = a.w;
+      tw[4] = b.x; tw[5] = b.y; tw[6] = b.z; tw[7] = b.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; i++) tw[i] = 0u;
+    }
+    if (mark) {
+      const uint4 c = *reinterpret_cast<const uint4 *>(mark + j0);
+      mw[0] = c.x; mw[1] = c.y; mw[2] = c.z; mw[3] = c.w;
+    }
+  } else {                                    // the last, partial chunk
+#pragma unroll
+    for (int i = 0; i < 8; i++) tw[i] = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; i++) mw[i] = 0u;
+    for (int i = 0; i < 16 && j0 + i < n; i++) {
+      if (tag) tw[i >> 1] |= (unsigned)tag[j0 + i] << (16 * (i & 1));
+      if (mark) mw[i >> 2] |= (unsigned)mark[j0 + i] << (8 * (i & 3));
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < 4; w++) kw[w] = 0u;
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const unsigned t = (tw[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+    const bool in = j0 + i < n;
+    // kind of a new point: PMMG_interpMetricsAndFields_mesh's dispatch
+    // (src/interpmesh_pmmg.c:541-560): !MG_VOK, MG_REQ (copied by
+    // PMMG_copyMetricsAndFields_point over every point, :311-446, whatever
+    // the tets), in no valid new tet (never visited), MG_BDY, volume
+    unsigned k = (t >= PMX_TAG_NUL) ? KIND_NUL
+                 : (t & PMX_TAG_REQ) ? KIND_SKIP
+                 : (mark && !((mw[i >> 2] >> (8 * (i & 3))) & 0xffu)) ? KIND_ORPH
+                 : (t & PMX_TAG_BDY) ? KIND_BDY : KIND_VOL;
+    k = in ? k : 0xffu;
+    cv += k == KIND_VOL;
+    cb += k == KIND_BDY;
+    kw[i >> 2] |= k << (8 * (i & 3));
+  }
+}
+
+// per tile of CLS_TILE points: how many volume / surface points
+__global__ __launch_bounds__(256) void k_cls_count(const uint16_t *__restrict__ tag, const uint8_t *__restrict__ mark,
+                                                   int64_t n, int2 *__restrict__ tcnt) {
+  __shared__ int2 red[4];
+  const int64_t t0 = (int64_t)blockIdx.x * CLS_TILE;
+  int cv = 0, cb = 0;
+#pragma unroll
+  for (int r = 0; r < CLS_TILE / 4096; r++) {
+    const int64_t j0 = t0 + r * 4096 + 16 * (int64_t)threadIdx.x;
+    unsigned kw[4];
+    if (j0 < n) kinds16(tag, mark, j0, n, kw, cv, cb);
+  }
+  const int2 c = block_sum2(make_int2(cv, cb), red);
+  if (threadIdx.x == 0) tcnt[blockIdx.x] = c;
+}
+
+// launch_classify that also carries the source vertices src[0..n) through the
+// compaction: vstart[j] / bstart[j] = the start element of the j-th volume /
+// surface point, vmap / tmap of its source, 1 when the source is outside
+// 1..np or no element holds it
+struct PointMapArgs {
+  const int *src;
+  const unsigned *vmap, *tmap;
+  int64_t np;
+  int *vstart, *bstart;
+};
+
+// kinds + the two lists in input order.  Per round of 4096 points: every
+// thread classifies 16 consecutive points (vector loads, one 16-B kind
+// store) into LDS; wave w owns points 1024 w .. 1024 w + 1023 of the round
+// (its own threads' chunks), so the wave totals give each wave its base, and
+// the wave then writes its list entries in 16 coalesced ballot sub-rounds.
+// Tile base = sum of the previous tiles' counts, summed again by every
+// workgroup (a few KB of L2 reads instead of a third launch).
+// PM (PMX_RUN_POINTMAP): the point's source vertex goes through the
+// compaction with it -- the start element of list entry j is resolved here
+// (one coalesced read of the sources, one gather of the map), so that the
+// walks read a coalesced int.
+// (The point-map arguments are a parameter pack: empty for the default
+// kernel, whose argument block and code stay what they were.)
+__device__ __forceinline__ const PointMapArgs &cls_pm(const PointMapArgs &a) { return a; }
+template <bool PM, class... PMA>
+__global__ __launch_bounds__(256) void k_cls_write(const uint16_t *__restrict__ tag,
+                                                   const uint8_t *__restrict__ mark, int64_t n,
+                                                   const int2 *__restrict__ tcnt, int8_t *__restrict__ kind,
+                                                   int *__restrict__ vlist, int *__restrict__ blist,
+                                                   int *__restrict__ nsel, PMA... pma) {
+  __shared__ int2 red[4];
+  __shared__ int2 wc[4];
+  __shared__ uint4 lk[256];                   // the round's 4096 kinds
+  int pv = 0, pb = 0;
+  for (unsigned t = threadIdx.x; t < blockIdx.x; t += 256) {
+    const int2 c = tcnt[t];
+    pv += c.x;
+    pb += c.y;
+  }
+  int2 base = block_sum2(make_int2(pv, pb), red);
+  const int64_t t0 = (int64_t)blockIdx.x * CLS_TILE;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const uint8_t *lkb = reinterpret_cast<const uint8_t *>(lk);
+  for (int r = 0; r < CLS_TILE / 4096; r++) {
+    const int64_t r0 = t0 + r * 4096;
+    if (r0 >= n) break;                                   // uniform: the tile's end
+    const int64_t j0 = r0 + 16 * (int64_t)threadIdx.x;
+    unsigned kw[4] = {~0u, ~0u, ~0u, ~0u};
+    int cv = 0, cb = 0;
+    if (j0 < n) {
+      kinds16(tag, mark, j0, n, kw, cv, cb);
+      if (j0 + 16 <= n) *reinterpret_cast<uint4 *>(kind + j0) = make_uint4(kw[0], kw[1], kw[2], kw[3]);
+      else
+        for (int i = 0; j0 + i < n; i++) kind[j0 + i] = (int8_t)((kw[i >> 2] >> (8 * (i & 3))) & 0xffu);
+    }
+    lk[threadIdx.x] = make_uint4(kw[0], kw[1], kw[2], kw[3]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      cv += __shfl_xor(cv, o, 64);
+      cb += __shfl_xor(cb, o, 64);
+    }
+    if (lane == 0) wc[w] = make_int2(cv, cb);
+    __syncthreads();
+    int ov = base.x, ob = base.y;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int2 c = wc[q];
+      ov += q < w ? c.x : 0;
+      ob += q < w ? c.y : 0;
+      base.x += c.x;
+      base.y += c.y;
+    }
+    // the wave's 1024 points in input order, 64 per sub-round
+#pragma unroll 4
+    for (int s = 0; s < 16; s++) {
+      const int p = 1024 * w + 64 * s + lane;
+      const int k = lkb[p];
+      const unsigned long long bv = __ballot(k == KIND_VOL), bb = __ballot(k == KIND_BDY);
+      if (k == KIND_VOL) vlist[ov + __popcll(bv & below)] = (int)(r0 + p);
+      else if (k == KIND_BDY) blist[ob + __popcll(bb & below)] = (int)(r0 + p);
+      if constexpr (PM) {
+        const PointMapArgs &pm = cls_pm(pma...);
+        if (k == KIND_VOL || k == KIND_BDY) {
+          const int sv = pm.src[r0 + p];
+          unsigned e = 0xffffffffu;
+          if (sv >= 1 && (int64_t)sv <= pm.np) e = (k == KIND_VOL ? pm.vmap : pm.tmap)[sv];
+          const int st = e == 0xffffffffu ? 1 : (int)e;     // the reference's initial start
+          if (k == KIND_VOL) pm.vstart[ov + __popcll(bv & below)] = st;
+          else pm.bstart[ob + __popcll(bb & below)] = st;
+        }
+      }
+      ov += __popcll(bv);
+      ob += __popcll(bb);
+    }
+    __syncthreads();                                      // lk and wc rewritten next round
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    nsel[0] = base.x;
+    nsel[1] = base.y;
+  }
+}
+
+static void launch_classify(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind, int *vlist,
+                            int *blist, int *nsel, hipStream_t s) {
+  if (n < 1) return;
+  const unsigned nt = (unsigned)cls_tiles(n);
+  hipLaunchKernelGGL(k_cls_count, dim3(nt), dim3(256), 0, s, tag, mk, n, tcnt);
+  hipLaunchKernelGGL((k_cls_write<false>), dim3(nt), dim3(256), 0, s, tag, mk, n, (const int2 *)tcnt, kind, vlist,
+                     blist, nsel);
+}
+static void launch_classify_pointmap(const uint16_t *tag, const uint8_t *mk, int64_t n, int2 *tcnt, int8_t *kind,
+                                     int *vlist, int *blist, int *nsel, const PointMapArgs &pm, hipStream_t s) {
+  if (n < 1) return;
+  const unsigned nt = (unsigned)cls_tiles(n);
+  hipLaunchKernelGGL(k_cls_count, dim3(nt), dim3(256), 0, s, tag, mk, n, tcnt);
+  hipLaunchKernelGGL((k_cls_write<true, PointMapArgs>), dim3(nt), dim3(256), 0, s, tag, mk, n, (const int2 *)tcnt,
+                     kind, vlist, blist, nsel, pm);
 }
 
 // ---- the new points ---------------------------------------------------------------

@@ -12,6 +12,9 @@
 //                         interpolation (src/libparmmg1.c:845), in the
 //                         device-resident interpolated metric (no re-upload)
 //
+// k_tet_conn           the statistics' connectivity stream (the tets' vertices,
+//                         16 B each) out of the tet records, built on demand
+//
 // The histogram is one pass over the mesh: per-thread accumulation, a
 // wavefront reduction, one partial record per workgroup, and a two-level final
 // reduction in workgroup order (deterministic sums).  This file also defines
@@ -254,6 +257,17 @@ __global__ __launch_bounds__(256) void k_count_nodes(const uint8_t *__restrict__
 // 256 CUs several times over, each a contiguous range of >= 2048 tets
 int stat_blocks(int64_t ne) {
   return (int)std::max<int64_t>(256, std::min<int64_t>(16384, ne / 2048));
+}
+
+// connectivity stream out of the tet records (statistics pass, built on demand)
+__global__ __launch_bounds__(256) void k_tet_conn(const TetRec *__restrict__ src, int64_t n,
+                                                  int4 *__restrict__ dst) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x)
+    dst[i] = *reinterpret_cast<const int4 *>(src + i);
+}
+static void launch_tet_conn(const TetRec *src, int64_t n, int4 *dst, hipStream_t s) {
+  hipLaunchKernelGGL(k_tet_conn, dim3(pmx_grid(n, 16384)), dim3(256), 0, s, src, n, dst);
 }
 
 bool ensure_tetv(pmx_ctx *ctx) {

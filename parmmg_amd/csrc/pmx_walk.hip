@@ -130,7 +130,7 @@ static int walk_layout(const SolDesc &sd, int *S) {
 }
 
 // Near-face cases of the canonical tie rule resolved in place (canonical_tet,
-// pmx_kernels.hip, is the general BFS over the containing set; this is the
+// pmx_fallback.hip, is the general BFS over the containing set; this is the
 // same rule for the two shapes that make up almost every tie):
 //  * no near face has an interior neighbour: the set is {cur};
 //  * exactly one near face f with neighbour n: the set is {cur} if n does not

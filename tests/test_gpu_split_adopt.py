@@ -100,7 +100,7 @@ def same_results(a, sa, b, sb):
     two walks started from the same element (starts(), recorded), and most
     starts agree; where they differ, located or not is equal.  The hint build
     leaves a volume walk's start to a plain store (any sampled tet of the cell;
-    pmx_kernels.hip), and in a group that is not convex the start decides
+    pmx_starts.hip), and in a group that is not convex the start decides
     whether the walk or the exhaustive scan finds the tet, the sign of status:
     point 375 of group 1 of k6_random5 came out 1 (2 steps) or -1 (5 steps) in
     5 of 60 step pairs between two contexts that uploaded the same mesh.  The
